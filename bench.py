@@ -2,6 +2,8 @@
 """bench.py — env-steps/sec of the batched GridworldCtf hot path on MI355X.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     # + per-kernel figures, roofline, secondaries, CPU baseline
+    python bench.py --gpus 1 --steps 200 --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus N --steps K --warmup W          # starts the N ranks itself (see launch_ranks below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W              # the driver's form: WORLD_SIZE must equal --gpus
@@ -9,17 +11,27 @@
 The N-worker launch this replaces is the reference's one Ray task per env (ppo.py:264-266, :349-376: ray_rollout.remote(env, agent,
 opponent) x num_envs, ray.get): here one process per GPU, each owning a contiguous range of global env indices.
 
+A plain run (no --full) does only what the headline needs: set up, warm up (W steps), time ONE window of exactly K steps, write
+the outputs if --dump-outputs is given, print the line.  --full adds everything else this file measures, as described below:
+the headline over `--windows` (5) windows, the per-kernel durations and roofline, the compact-observation rate, the `secondary`
+blocks and the `cpu_baseline`.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: `rewards` [E, N] and `done` [E] of every env
+of rank 0's shard (sampled like the observations when they would exceed 16 MiB), and `obs` [S, N, C, G, G] / `meta` [S, N, 2N+6]
+of a fixed sample of S = min(E, 256) envs (np.random.default_rng(DUMP_SEED).choice(E, S, replace=False), sorted).  Same arguments,
+same inputs: seeds and action streams are functions of --run and the global env index, so two builds compare output for output.
+
 One "step" = one pass of the hot path over one batch: GridworldCtf.step() for every env of the shard
 plus the N observations + metadata rows a rollout consumes (reference ppo.py:59-98), with auto-reset at
 episode end — the two launches of ctf_step_observe (k_step, whose tail blocks regenerate the MT19937 blocks the
-envs have used up, then the render).  The timed region holds nothing else: `--windows` (5) back-to-back windows of
-exactly K such steps, each bracketed by barrier + synchronize, MAX over ranks per window; `ms_per_step` / `value` are
-those of the MEDIAN window (`windows_ms` lists them all).  The per-kernel durations come from SAMPLE_STEPS (12) further
+envs have used up, then the render).  The timed region holds nothing else: `--windows` back-to-back windows (1 in a plain run, 5
+with --full) of exactly K such steps, each bracketed by barrier + synchronize, MAX over ranks per window; `ms_per_step` / `value`
+are those of the MEDIAN window (`windows_ms` lists them all).  With --full the per-kernel durations come from SAMPLE_STEPS (12) further
 steps AFTER the windows, issued as ctf_step + ctf_observe with a HIP event around each launch, net of the cost of an
 empty event pair measured in the same run (`event_pair_overhead_ms`).  Workload at N=1: BASELINE.json configs[2] — 8_arena
 (arena_iii, 4v4, the reference's 15x15 map), 65 536 envs resident in HBM; N>1 keeps 65 536 envs per GPU
-(weak scaling) in the headline and adds, as `secondary.configs3_262144`, BASELINE.json configs[3] at its own size
-(262 144 envs GLOBAL = 262 144 / N per GPU: the strong-scaling reading of the same path); the N=1 line carries that
+(weak scaling) in the headline and, with --full, adds, as `secondary.configs3_262144`, BASELINE.json configs[3] at its own size
+(262 144 envs GLOBAL = 262 144 / N per GPU: the strong-scaling reading of the same path); the N=1 --full line carries that
 configuration's per-GPU shard of an 8-GPU job as `secondary.arena_32768`.  Envs are sharded by global index with no data-path collective (--rollout-exchange adds an
 asynchronous RCCL all-gather of the compact rollout tensors once per 16-step chunk, what a centralised
 learner would need).  Inputs (Philox action streams for every timed step) are generated on the device
@@ -31,7 +43,7 @@ holds the steady-state mix: ~E/500 envs reach GAME_STEPS and are reset inside th
 agents are spread over the map, tags / respawns / flag events occur at their steady-state rates.  (The
 511-step visitation-log fold cannot occur under this protocol: an episode ends at 500 steps.)
 
-At N=1 the line also carries, as `secondary`, the other single-GPU BASELINE configurations run the same
+With --full, at N=1 the line also carries, as `secondary`, the other single-GPU BASELINE configurations run the same
 way — the synthetic 20x20 arena at 65 536 envs (BASELINE.json's wording) and 0_the_split at 4 096 envs
 (configs[1]) — each with its own roofline.
 
@@ -356,16 +368,34 @@ def two_shards_two_streams(pkg, torch, name, E, K, W, local_rank, run, windows=5
 
 
 SAMPLE_STEPS = 12  # steps run AFTER the timed windows with an event around each launch (the per-kernel durations)
+DUMP_SEED, DUMP_ENVS = 0xD0, 256  # --dump-outputs: the fixed sample of envs whose observations are written
+DUMP_FULL_LIMIT = 16 << 20  # rewards + done of every env while they fit in this many bytes (float32), else the sample's
+
+
+def snapshot_outputs(torch, vec):
+    """What the caller of the timed path holds after its last step (ctf_step_observe's rewards, done, obs, meta), as float32 host
+    arrays: rewards / done of every env, obs / meta of a fixed, seeded sample of envs (see the module docstring)."""
+    import numpy as np
+
+    E, N = vec.n_envs, vec.N_AGENTS
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(E, min(E, DUMP_ENVS), replace=False))
+    idx = torch.from_numpy(pick).to(vec.device)
+    host = lambda t: t.float().cpu().numpy()
+    full = E * (N + 1) * 4 <= DUMP_FULL_LIMIT
+    return {"rewards": host(vec.rewards if full else vec.rewards.index_select(0, idx)),
+            "done": host(vec.done if full else vec.done.index_select(0, idx)),
+            "obs": host(vec.obs.index_select(0, idx)), "meta": host(vec.meta.index_select(0, idx))}
 
 
 def run_workload(pkg, torch, name, E, K, W, rank, local_rank, world, run, log_metrics=True, stagger=True, gather=None, dist=None,
-                 extras=True, rng_mode="mt19937", windows=5, env_lo=None):
+                 extras=True, rng_mode="mt19937", windows=5, env_lo=None, kernel_sample=True, capture=False):
     """-> dict of this rank's measurements of one workload.
 
     Timed region: `windows` back-to-back windows, each EXACTLY K calls of ctf_step_observe and nothing else (no event records, no
-    host reads), bracketed by barrier + synchronize on both sides.  The per-kernel durations are taken afterwards, in SAMPLE_STEPS
-    further steps of the same trajectory issued as ctf_step + ctf_observe with an event around each launch and one empty event
-    pair per step (what a pair costs by itself in this stream state: subtracted from the raw figures)."""
+    host reads), bracketed by barrier + synchronize on both sides.  With `capture`, the outputs of the last timed step are copied to
+    the host right after it (snapshot_outputs -> "outputs").  With `kernel_sample` the per-kernel durations are taken afterwards, in
+    SAMPLE_STEPS further steps of the same trajectory issued as ctf_step + ctf_observe with an event around each launch and one
+    empty event pair per step (what a pair costs by itself in this stream state: subtracted from the raw figures)."""
     import numpy as np
 
     sh = pkg.sharding
@@ -419,6 +449,14 @@ def run_workload(pkg, torch, name, E, K, W, rank, local_rank, world, run, log_me
         win.append(time.perf_counter() - t0)
         t += K
     status = vec.status()
+    outputs = snapshot_outputs(torch, vec) if capture else None
+    out = dict(name=name, label=label, E=E, N=N, G=G, C=C, K=K, W=W, windows=win, env_lo=lo, status=status, outputs=outputs,
+               placement_probe_ms=vec.placement_probe_ms, placement_fill_ms=vec.placement_fill_ms, placement=vec.placement, kwargs=kwargs)
+    if not kernel_sample:
+        vec.close()
+        del vec, actions
+        torch.cuda.empty_cache()
+        return out
 
     # ---- after the timed region: per-kernel durations
     fill(t, SAMPLE_STEPS)
@@ -437,14 +475,12 @@ def run_workload(pkg, torch, name, E, K, W, rank, local_rank, world, run, log_me
     step_raw = np.array([e[0].elapsed_time(e[1]) for e in ev])
     obs_raw = np.array([e[1].elapsed_time(e[2]) for e in ev])
     step_all, obs_all = np.maximum(step_raw - pair, 0.0), np.maximum(obs_raw - pair, 0.0)
-    out = dict(name=name, label=label, E=E, N=N, G=G, C=C, K=K, W=W, windows=win, env_lo=lo, status=status | vec.status(),
-               observe_kernel=observe_kernel, observe_stores=observe_stores,
+    out.update(status=status | vec.status(), observe_kernel=observe_kernel, observe_stores=observe_stores,
                k_step_ms=float(step_all.mean()), k_observe_ms=float(obs_all.mean()),
                k_step_raw_ms=float(step_raw.mean()), k_observe_raw_ms=float(obs_raw.mean()), event_pair_ms=pair,
                k_step_p=[float(x) for x in np.percentile(step_all, [10, 50, 90])],
                k_observe_p=[float(x) for x in np.percentile(obs_all, [10, 50, 90])],
-               kernel_timing_samples=len(ev), placement_probe_ms=vec.placement_probe_ms, placement_fill_ms=vec.placement_fill_ms,
-               placement=vec.placement, kwargs=kwargs)
+               kernel_timing_samples=len(ev))
     if extras:
         # outside the timed region: the same env-step with the observation in compact form (ctf_observe_codes: one byte per
         # cell instead of C one-hot bytes — what the GPU policy path consumes)
@@ -478,10 +514,24 @@ def dryrun_workload(pkg, name, E, K, W, rank, dist, windows=5, env_lo=None):
         if dist is not None:
             dist.barrier()
     return dict(name=name, label=label, E=E, N=cfg.n_agents, G=cfg.grid_size, C=cfg.n_channels, K=K, W=W, windows=win,
-                env_lo=rank * E if env_lo is None else env_lo, status=0,
+                env_lo=rank * E if env_lo is None else env_lo, status=0, outputs=None,
                 observe_kernel="none (dry run)", observe_stores="none (dry run)", k_step_ms=0.25, k_observe_ms=0.75, k_step_raw_ms=0.25, k_observe_raw_ms=0.75,
                 event_pair_ms=0.0, k_step_p=[0.25] * 3, k_observe_p=[0.75] * 3,
                 kernel_timing_samples=0, placement_probe_ms=None, placement_fill_ms=None, placement=None, kwargs=kwargs)
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: the arrays of snapshot_outputs as path/<name>.npy (a dry run has none to write)."""
+    import numpy as np
+
+    if outputs is None:
+        print("[bench.py] --dump-outputs: a dry run computes no outputs; nothing written", file=sys.stderr, flush=True)
+        return
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench.py] wrote {', '.join(f'{k}{list(a.shape)}' for k, a in outputs.items())} "
+          f"({sum(a.nbytes for a in outputs.values()) / 2**20:.1f} MiB) to {path}", file=sys.stderr, flush=True)
 
 
 def reduce_windows(sh, r, device, world, use_dist):
@@ -557,10 +607,18 @@ def main():
     ap.add_argument("--env-offset", type=int, default=0,
                     help="global index of the job's first env (rank r owns [offset + r * E, offset + (r + 1) * E)): e.g. 98304 with "
                          "--envs-per-gpu 32768 is the shard of rank 3 of 8 of configs[3]")
-    ap.add_argument("--windows", type=int, default=5, help="back-to-back timed windows of --steps steps each; the line reports the median one")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="back-to-back timed windows of --steps steps each; the line reports the median one (default: 1, with --full 5)")
     ap.add_argument("--configs3-envs", type=int, default=262144,
                     help="GLOBAL env count of the N>1 secondary (BASELINE.json configs[3]: 262 144 envs over the N GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: 5 timed windows, per-kernel durations and roofline, the compact "
+                         "observation rate, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; rank 0's shard; see the module docstring)")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     rc = world_or_launch(args.gpus, os.path.abspath(__file__), sys.argv[1:])
     if rc is not None:  # this process was the launcher of the N ranks; their rank 0 has printed the line
@@ -615,7 +673,7 @@ def main():
     exchange = use_dist and args.rollout_exchange
     n_agents = len(WORKLOADS[args.workload][1](pkg)["AGENT_CONFIG"])
 
-    def measure(name, e_rank, k, env_lo=None, use_gather=False, extras=False, rng_mode="mt19937"):
+    def measure(name, e_rank, k, env_lo=None, use_gather=False, extras=False, rng_mode="mt19937", capture=False):
         """One workload on EVERY rank of the job (a collective call: barriers inside) -> this rank's record with the job-wide
         window times (reduce_windows)."""
         g = sh.ChunkedRolloutGather(e_rank, n_agents, device, world, chunk=16, force_collective=exchange) if use_gather else None
@@ -624,10 +682,11 @@ def main():
         else:
             r = run_workload(pkg, torch, name, e_rank, k, W, rank, local_rank, world, args.run, log_metrics=not args.no_metrics,
                              stagger=not args.no_stagger, gather=g, dist=dist, extras=extras, rng_mode=rng_mode, windows=args.windows,
-                             env_lo=env_lo)
+                             env_lo=env_lo, kernel_sample=args.full, capture=capture)
         return reduce_windows(sh, r, device, world, use_dist)
 
-    r = measure(args.workload, E, K, env_lo=args.env_offset + rank * E, use_gather=exchange, extras=(rank == 0))
+    r = measure(args.workload, E, K, env_lo=args.env_offset + rank * E, use_gather=exchange, extras=(rank == 0 and args.full),
+                capture=(rank == 0 and args.dump_outputs is not None))
     elapsed = r["elapsed"]
     ranks_seen, per_rank_ms = sh.gather_rank_times(rank, r["my_ms"], world if use_dist else 1)
     # a multi-GPU line must verify itself: every rank of the job reported a time, exactly once
@@ -636,14 +695,12 @@ def main():
     # BASELINE.json configs[3] at ITS OWN size: 262 144 envs GLOBAL, sharded by global env index over the N ranks of this job
     # (strong scaling: 262 144 / N per GPU; 32 768 at N = 8).  Every rank runs it (barriers inside), rank 0 reports it.
     r3 = None
-    if world > 1 and args.workload == "arena" and not args.no_secondary:
+    if args.full and world > 1 and args.workload == "arena" and not args.no_secondary:
         lo3, hi3 = sh.shard_range(args.configs3_envs, rank, world)
         r3 = measure("arena", hi3 - lo3, max(20, min(K, 100)), env_lo=lo3)
         r3["shards"] = [list(sh.shard_range(args.configs3_envs, q, world)) for q in range(world)]
 
     if rank == 0:
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        traffic_table = json.load(open(tpath)) if os.path.exists(tpath) else {}
         N, G, C = r["N"], r["G"], r["C"]
         value = n_gpus * E * K / elapsed
         line = {
@@ -675,13 +732,9 @@ def main():
                                 "barrier + synchronize on both sides of each, MAX over ranks per window; value / ms_per_step = the MEDIAN window",
             },
         }
-        blk = workload_block(r, value, traffic_table, n_gpus)
-        for k in ("windows", "windows_ms_per_step", "roofline", "whole_step_hbm_frac", "kernels_ms", "render_stores", "kernels_ms_raw_events",
-                  "event_pair_overhead_ms", "kernels_ms_p10_p50_p90", "kernel_timing_samples", "kernel_timing"):
-            line[k] = blk[k]
         line.update({
-            "step_kernel_gbs": step_algorithmic_bytes(N, G) * E / (r["k_step_ms"] * 1e-3) / 1e9 if r["k_step_ms"] > 0 else None,
-            "episode_phase_spread": r.get("episode_phase_spread"),
+            "windows": len(r["windows_max"]),
+            "windows_ms_per_step": [w / K * 1e3 for w in r["windows_max"]],
             # where the observation buffer landed: a box whose allocations are all of the slow kind explains its
             # own lower number here — kind, the render's time over a plain fill of the same buffer, the slowest candidate seen
             "placement": r["placement"],
@@ -691,9 +744,23 @@ def main():
             "ranks_ok": ranks_ok,
             "ranks_seen": sorted(ranks_seen),
             "per_rank_ms_per_step": [per_rank_ms[ranks_seen.index(k)] for k in sorted(ranks_seen)],
-            "compact_observation": {"env_steps_per_s_per_gpu": r.get("compact_rate"), "obs_bytes_per_env": N * G * G + N * (2 * N + 6) * 2,
-                                    "note": "step() + observe_codes(); not the headline metric (the reference's consumers take the one-hot planes)"},
+            "full": args.full,
         })
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, r["outputs"])
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        traffic_table = json.load(open(tpath)) if args.full and os.path.exists(tpath) else {}
+        if args.full:
+            blk = workload_block(r, value, traffic_table, n_gpus)
+            for k in ("roofline", "whole_step_hbm_frac", "kernels_ms", "render_stores", "kernels_ms_raw_events",
+                      "event_pair_overhead_ms", "kernels_ms_p10_p50_p90", "kernel_timing_samples", "kernel_timing"):
+                line[k] = blk[k]
+            line.update({
+                "step_kernel_gbs": step_algorithmic_bytes(N, G) * E / (r["k_step_ms"] * 1e-3) / 1e9 if r["k_step_ms"] > 0 else None,
+                "episode_phase_spread": r.get("episode_phase_spread"),
+                "compact_observation": {"env_steps_per_s_per_gpu": r.get("compact_rate"), "obs_bytes_per_env": N * G * G + N * (2 * N + 6) * 2,
+                                        "note": "step() + observe_codes(); not the headline metric (the reference's consumers take the one-hot planes)"},
+            })
         sec = {}
         if r3 is not None:
             g3 = args.configs3_envs
@@ -706,7 +773,7 @@ def main():
                 "scaling": "strong",
             })
             sec[f"configs3_{g3}"] = b3
-        if n_gpus == 1 and not args.no_secondary and args.workload == "arena" and not dryrun:
+        if args.full and n_gpus == 1 and not args.no_secondary and args.workload == "arena" and not dryrun:
             # (a) the per-GPU shard of configs[3] on an 8-GPU node — 32 768 envs, created here as "rank 3 of 8" (global envs
             # [98 304, 131 072)); (b) the synthetic 20x20 arena; (c) configs[1], 0_the_split at 4 096 envs
             for key, name, e2, lo2 in (("arena_32768", "arena", 32768, 3 * 32768), ("arena20_65536", "arena20", 65536, None),
@@ -743,7 +810,7 @@ def main():
             sec["ppo_selfplay_65536x500"] = selfplay_at_reference_length(torch, local_rank, time.perf_counter() - t_start)
         if sec:
             line["secondary"] = sec
-        if n_gpus == 1 and not args.no_cpu_baseline and not dryrun:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and not dryrun:
             line["cpu_baseline"] = cpu_baseline(pkg, r["kwargs"])
         line["wall_s"] = time.perf_counter() - t_start
         sys.stdout.flush()

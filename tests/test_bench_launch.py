@@ -26,7 +26,7 @@ def _one_json_line(stdout):
 
 
 def test_gpus_2_without_torchrun_starts_two_ranks():
-    r = _run("bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1")
+    r = _run("bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     line = _one_json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == [0, 1] and line["ranks_ok"] is True
@@ -43,7 +43,7 @@ def test_gpus_2_without_torchrun_starts_two_ranks():
 def test_gpus_2_line_carries_configs3_at_its_own_global_size():
     """BASELINE.json configs[3] is 262 144 envs GLOBAL: besides the weak-scaling headline (65 536 per GPU) an N-rank line holds
     `secondary.configs3_262144`, 262 144 / N envs per rank, sharded by global env index (sharding.shard_range)."""
-    r = _run("bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1")
+    r = _run("bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     c3 = _one_json_line(r.stdout)["secondary"]["configs3_262144"]
     assert c3["global_envs"] == 262144 and c3["envs_per_gpu"] == [131072, 131072] and c3["shards"] == [[0, 131072], [131072, 262144]]
@@ -51,11 +51,11 @@ def test_gpus_2_line_carries_configs3_at_its_own_global_size():
     assert c3["value"] == pytest.approx(262144 / (c3["ms_per_step"] * 1e-3)) and c3["ms_per_step"] == pytest.approx(2.02)
     assert c3["roofline"]["algorithmic_bytes_per_env"] == 25878
     # an odd global size is split by the same rule the learner and the tests use
-    r = _run("bench.py", "--gpus", "2", "--steps", "2", "--warmup", "0", "--configs3-envs", "1001")
+    r = _run("bench.py", "--gpus", "2", "--steps", "2", "--warmup", "0", "--configs3-envs", "1001", "--full")
     c3 = _one_json_line(r.stdout)["secondary"]["configs3_1001"]
     assert c3["envs_per_gpu"] == [501, 500] and c3["global_envs"] == 1001
     # N = 1 is not configs[3]: no such block (its shard rides as secondary.arena_32768 on a GPU)
-    r = _run("bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0")
+    r = _run("bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--full")
     assert "secondary" not in _one_json_line(r.stdout)
 
 
@@ -65,6 +65,24 @@ def test_gpus_1_is_one_rank_in_process():
     line = _one_json_line(r.stdout)
     assert line["n_gpus"] == 1 and line["ranks_seen"] == [0]
     assert "starting" not in r.stderr  # no launcher
+
+
+def test_a_plain_run_times_exactly_steps_and_nothing_else():
+    """Without --full the line is the headline alone: ONE window of exactly --steps steps (ms_per_step = that window / K), no
+    per-kernel sample, roofline, secondary or CPU baseline; every rank still reports."""
+    r = _run("bench.py", "--gpus", "2", "--steps", "7", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _one_json_line(r.stdout)
+    assert line["steps"] == 7 and line["windows"] == 1 and line["full"] is False and line["ranks_seen"] == [0, 1]
+    assert line["windows_ms_per_step"] == pytest.approx([2.04]) and line["ms_per_step"] == pytest.approx(2.04)
+    assert line["value"] == pytest.approx(2 * 65536 / 2.04e-3)
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert key in line
+    for key in ("secondary", "cpu_baseline", "roofline", "kernels_ms", "compact_observation"):
+        assert key not in line, key
+    # --windows still sets the number of windows of a plain run
+    line = _one_json_line(_run("bench.py", "--gpus", "1", "--steps", "3", "--warmup", "0", "--windows", "3").stdout)
+    assert line["windows"] == 3 and line["steps"] == 3
 
 
 def test_world_size_that_contradicts_gpus_is_refused():

@@ -27,7 +27,7 @@ def _run(script, *argv, timeout=900):
 
 
 def test_bench_with_two_ranks_on_one_gpu():
-    line = _run("bench.py", "--gpus", "2", "--envs-per-gpu", "8192", "--steps", "40", "--warmup", "5", "--no-cpu-baseline")
+    line = _run("bench.py", "--gpus", "2", "--envs-per-gpu", "8192", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--full")
     assert line["n_gpus"] == 2 and line["ranks_seen"] == [0, 1] and line["ranks_ok"] is True
     assert line["config"]["global_envs"] == 2 * 8192 and line["config"]["ranks_share_one_device"] is True
     assert line["device_status_bits"] == 0 and len(line["per_rank_ms_per_step"]) == 2 and min(line["per_rank_ms_per_step"]) > 0

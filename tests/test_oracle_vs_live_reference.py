@@ -1,13 +1,11 @@
-"""The C oracle against the LIVE reference on fresh random configurations (build container only: it imports /root/reference).
-
-The committed fixtures (tests/golden/*.npz) pin the oracle on 62 recorded trajectories; this test draws NEW small maps and rule
-combinations every run of the generator seed list below — the fuzz the round-4 review ran by hand (120 configs, 0 mismatches) kept as a
-test: per step grid, positions, f64 hp, flags, inventory, `_arr`, f64 rewards, done, both MT positions, all N observations and metadata
-rows; at the end counters, visitation maps and both generators' full states.  A config on which the reference itself raises (no open
-respawn cell: ValueError from np.random.randint(0)) must make the oracle report CTF_ST_NO_RESPAWN at the same step."""
-import importlib
+"""The C oracle against the reference on random configurations: the fuzz the round-4 review ran by hand (120 configs, 0 mismatches)
+kept as a test.  The configurations and action tapes are drawn from fixed seeds (tests/golden/make_golden_live.py draw_trials); what the
+reference did on each — per step grid, positions, f64 hp, flags, inventory, `_arr`, f64 rewards, done, both MT positions, all N
+observations and metadata rows; at the end counters, visitation maps and both generators' full states — is recorded in
+tests/golden/live/reference.npz (per-step 64-bit digests, end-of-trial arrays in full; re-recorded from the reference by that script).
+A config on which the reference itself raises (no open respawn cell: ValueError from np.random.randint(0)) must make the oracle
+report CTF_ST_NO_RESPAWN at the same step."""
 import os
-import random
 import sys
 
 import numpy as np
@@ -15,67 +13,42 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-import _refimport  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not _refimport.available(), reason="/root/reference is present in the build container only")
+import make_golden_live as live  # noqa: E402
 
 import oracle  # noqa: E402
-from _cases import abi, cfgmod, view_arrays, wild_config  # noqa: E402
+from _cases import abi, cfgmod, view_arrays  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def ref():
-    cwd = os.getcwd()
-    Ref, scn = _refimport.import_reference()
-    yield Ref
-    os.chdir(cwd)
+    with np.load(live.OUT) as z:
+        return {k: z[k] for k in z.files}
 
 
-def _random_case(rng):
-    import make_golden_fuzz as mgf
-
-    scen, agents = mgf.random_scenario(rng, "Live")
-    pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
-    hp = pick([0.25, 0.5, 1.0])
-    kw = dict(GRID_SIZE=scen["GRID_SIZE"], AGENT_CONFIG=agents, GAME_STEPS=int(rng.integers(40, 121)), MAP_SYMMETRY_CHECK=False,
-              HOME_FLAG_CAPTURE=bool(rng.integers(0, 2)), DROP_FLAG_WHEN_NO_HP=bool(rng.integers(0, 2)),
-              USE_ADJUSTED_REWARDS=bool(rng.integers(0, 2)), TAG_PROBABILITY=pick([0.2, 0.5, 0.9, 1.0]),
-              AGENT_TYPE_HP={0: 10 * hp, 1: 8 * hp, 2: 8 * hp, 3: 7 * hp}, AGENT_TYPE_DAMAGE={0: 1, 1: 0.5, 2: 0.5, 3: 1},
-              GUARDIAN_DAMAGE_MULTIPLIER=pick([1.0, 5.0]), VAULT_HP_COST=pick([0.25, 1.25]), VAULT_MIN_HP=pick([0.5, 2.5]),
-              AGENT_HP_HEALING_PER_STEP=pick([0.0, 0.1, 0.25]))
-    return scen, kw
-
-
-@pytest.mark.parametrize("block", list(range(12)) + [f"wild{k}" for k in range(12)])
+@pytest.mark.parametrize("block", live.BLOCKS)
 def test_oracle_equals_the_live_reference_on_random_configurations(ref, block):
     """Blocks 0-11: capture-dense small maps in the style of the committed fuzz fixtures.  Blocks wild0-11: configurations outside what the
     shipped maps use (tests/_cases.py wild_config: unequal teams, capture cells away from the flags, no-damage types, TAG_PROBABILITY 0,
     healing past the cap, 4x4 grids with eight agents ...): 10 of each per block."""
     wild = isinstance(block, str)
-    rng = np.random.default_rng(888_000 + int(block[4:])) if wild else np.random.default_rng(777_000 + block)
     captures = raised = 0
-    for trial in range(10):
-        drawn = wild_config(rng) if wild else _random_case(rng)
-        if drawn is None:
-            continue
-        scen, kw = drawn
-        seed = int(rng.integers(0, 2 ** 31))
-        n = len(kw["AGENT_CONFIG"])
-        T = kw["GAME_STEPS"] + 5
-        actions = np.where(rng.random((T, n)) < 0.15, rng.integers(5, 9, (T, n)), rng.integers(0, 5, (T, n))).astype(np.int8)
-        random.seed(seed)
-        np.random.seed(seed)
-        env = ref(SCENARIO=scen, **kw)
+    trials = live.draw_trials(block)
+    assert {k for k in ref if k.startswith(f"b{block}_")} == {live.key(block, tr[0], w) for tr in trials for w in ("tiles_used", "raised", "states", "views")} | {
+        live.key(block, tr[0], w) for tr in trials if int(ref[live.key(block, tr[0], "raised")]) < 0 for w in ("metrics", "visitation", "team_captures", "rng_states")}
+    for trial, scen, kw, seed, actions in trials:
+        rec = lambda what: ref[live.key(block, trial, what)]
+        n, T = len(kw["AGENT_CONFIG"]), len(actions)
         cfg, derived = cfgmod.build_config(dict(kw, SCENARIO=scen), log_metrics=True)
-        assert derived["tiles_used"] == [int(x) for x in env.TILES_USED]
+        assert derived["tiles_used"] == rec("tiles_used").tolist()
         o = oracle.OracleEnv(cfg)
         o.seed(seed, seed)
-        g, teams = env.GRID_SIZE, [env.AGENT_TEAMS[i] for i in range(n)]
+        g = kw["GRID_SIZE"]
         ctx = f"block {block} trial {trial} seed {seed}"
+        stop, states, views = int(rec("raised")), rec("states"), rec("views")
+        assert len(states) == (stop if stop >= 0 else T), ctx
+        v = 0
         for t in range(T):
-            try:
-                _, rewards, done = env.step([int(a) for a in actions[t]])
-            except ValueError:  # the reference's own failure: no open cell round the spawn
+            if t == stop:  # the reference's own failure: no open cell round the spawn
                 _, _, status = o.step(actions[t])
                 assert status & abi.ST_NO_RESPAWN, ctx
                 raised += 1
@@ -83,27 +56,20 @@ def test_oracle_equals_the_live_reference_on_random_configurations(ref, block):
             rw, dn, status = o.step(actions[t])
             assert status == 0, (ctx, t, status)
             s = view_arrays(o.get_state(), n, g)
-            where = f"{ctx} step {t}"
-            assert np.array_equal(s["grid"], env.grid), where
-            assert s["pos"].tolist() == [list(env.agent_positions[i]) for i in range(n)], where
-            assert s["hp"].tolist() == [float(env.agent_hp[i]) for i in range(n)], where
-            assert np.array_equal(s["has_flag"], env.has_flag) and s["inv"].tolist() == [env.block_inventory[i] for i in range(n)], where
-            assert s["perm"].tolist() == list(env._arr) and rw.tolist() == [float(r) for r in rewards] and dn == done, where
             py, npw = o.get_rng_state()
-            assert int(py[624]) == random.getstate()[1][624] and int(npw[624]) == np.random.get_state()[2], where + " (draw counts)"
-            if t % 3 == 0 or t == T - 1:
+            got = live.state_digest(s["grid"], s["pos"], s["hp"], s["has_flag"], s["inv"], s["perm"], rw, dn, py[624], npw[624])
+            assert got == states[t], f"{ctx} step {t}: grid / positions / hp / flags / inventory / _arr / rewards / done / MT positions"
+            if live.observed(t, T):
                 obs, meta = o.observe()
-                want_o = np.stack([env.standardise_state(i, reverse_grid=teams[i] == 1)[0] for i in range(n)])
-                want_m = np.stack([env.get_env_metadata(i)[0] for i in range(n)])
-                assert np.array_equal(obs, want_o) and np.array_equal(meta.view(np.uint16), want_m.view(np.uint16)), where
+                assert live.obs_digest(obs, meta) == views[v], f"{ctx} step {t}: observations / metadata"
+                v += 1
         else:
+            assert v == len(views), ctx
             s = view_arrays(o.get_state(), n, g)
-            for k, name in enumerate(abi.METRIC_NAMES):
-                assert s["metrics"][k].tolist() == [env.metrics["agent_" + name].get(i, 0) for i in range(n)], (ctx, name)
-            assert np.array_equal(s["visitation"], np.stack([env.metrics["agent_visitation_maps"][i] for i in range(n)])), ctx
-            assert s["team_captures"] == [env.metrics["team_flag_captures"][0], env.metrics["team_flag_captures"][1]]
+            assert np.array_equal(s["metrics"], rec("metrics")), ctx
+            assert np.array_equal(s["visitation"], rec("visitation")), ctx
+            assert s["team_captures"] == rec("team_captures").tolist(), ctx
             py, npw = o.get_rng_state()
-            st = np.random.get_state()
-            assert py.tolist() == list(random.getstate()[1]) and np.array_equal(npw[:624], st[1]) and int(npw[624]) == st[2], ctx
+            assert live.rng_digest(py, npw[:624], npw[624]) == rec("rng_states")[0], ctx
             captures += sum(s["team_captures"])
     assert wild or captures + raised > 0  # (a capture-dense block without a single capture or respawn failure would not be testing much)

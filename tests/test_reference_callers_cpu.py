@@ -204,7 +204,10 @@ def test_the_references_whole_training_loop_trains_the_same_network_on_both_clas
     assert rg[0] == rw[0] and np.array_equal(rg[1], rw[1]) and rg[2] == rw[2] and torch.equal(tw, tg)
 
 
-SCRIPTS = sorted(f for f in os.listdir(_refimport.REFERENCE_DIR) if f[0].isdigit() and f.endswith(".py")) if _refimport.available() else []
+# The reference's experiment scripts, named here so that the cases are the same wherever the suite is collected (with or without the
+# reference); every case checks that this list is still the reference's whole set of numbered scripts.
+SCRIPTS = ["0_the_split.py", "1_fence.py", "2_jailbreak.py", "3_one_way_out.py", "4_keyhole.py", "5_skittles.py", "6_the_wall.py",
+           "7_gridlocked.py", "8_arena.py"]
 
 
 @pytest.mark.parametrize("script", SCRIPTS)
@@ -217,6 +220,7 @@ def test_an_experiment_script_runs_its_whole_league_pipeline_unchanged_on_both_c
     GridworldCtf``).  Same seeds: the trained network, the win-rate matrices, every harvested metric and the reward history are equal."""
     import importlib.util
 
+    assert sorted(f for f in os.listdir(_refimport.REFERENCE_DIR) if f[0].isdigit() and f.endswith(".py")) == SCRIPTS
     mods = _refimport.import_reference.modules
     ray = sys.modules["ray"]
     monkeypatch.setattr(ray, "remote", lambda f: types.SimpleNamespace(remote=f), raising=False)
