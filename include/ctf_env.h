@@ -51,6 +51,8 @@ extern "C" {
 #define CTF_ST_SPAWN_EDGE 4u   /* respawn offset went negative (spawn on row/col 0, the WARNING at :773) */
 #define CTF_ST_RNG_OVERRUN 8u  /* one step drew more than ~624 words from one generator: its rejection loops cannot be
                                   followed further (a run of > 500 rejected draws: does not happen)                  */
+#define CTF_ST_SYNC_TIMEOUT 16u /* ctf_step_observe's single launch: a render tile waited longer than its bound (10 ms) for
+                                   the step of its envs and went on (the launch's blocks did not run in index order)  */
 
 /* ctf_config.rng_mode */
 #define CTF_RNG_MT19937 0 /* the reference's two MT19937 generators, bit for bit (default)                          */
@@ -234,12 +236,16 @@ int ctf_observe_codes(ctf_env* env, uint8_t* codes_dev, uint16_t* meta_dev, uint
                       void* stream);
 
 /* ctf_step immediately followed by ctf_observe (the rollout inner loop, ppo.py:59-98): the two launches enqueued by one
- * call.  (A single fused launch was built and measured in round 2 — bit-exact but 25 % slower, because a group's step
- * is an ~85 us dependent chain that only the step kernel's "every group in flight at once" shape hides:
- * profiles/r02_fused_step_observe_ablation.md.) */
+ * call.  With CTF_STEP_OBSERVE_ONE_LAUNCH=1, where the tile render applies (ctf_observe_kernel == 1), ONE launch instead,
+ * k_step_observe: the step's blocks, its ring regeneration, then the render's tiles, each of which waits only for the step
+ * blocks of its own (one or two) envs — the same results bit for bit, but 9 % slower at 65 536 arena envs, so not the
+ * default (profiles/r06_one_launch_step_observe.md).  (Step and render fused per env group, one wave doing
+ * both, was measured in round 2 — 25 % slower: profiles/r02_fused_step_observe_ablation.md.) */
 int ctf_step_observe(ctf_env* env, const int8_t* actions_dev, float* rewards_f32_dev,
                      double* rewards_f64_dev, uint8_t* done_dev, uint8_t* obs_dev, uint16_t* meta_dev,
                      uint32_t reverse_mask, uint32_t flags, void* stream);
+/* how many launches a ctf_step_observe into obs_dev makes now: 1 (k_step_observe) or 2 (k_step, then ctf_observe's kernel) */
+int32_t ctf_step_observe_launches(const ctf_env* env, const uint8_t* obs_dev);
 
 /* AGENT_TYPE_ACTION_MASK expanded as agent_network.py:66-75 does: mask_host[i][a] = 1 if action a is
  * legal for agent i (flag 1 => actions 0..4 only).  Host buffer uint8 [N][9]. */

@@ -19,6 +19,7 @@ ST_BAD_ACTION = 1
 ST_NO_RESPAWN = 2
 ST_SPAWN_EDGE = 4
 ST_RNG_OVERRUN = 8
+ST_SYNC_TIMEOUT = 16
 STEP_AUTO_RESET = 1
 RNG_MT19937 = 0
 RNG_COUNTER = 1
@@ -128,6 +129,7 @@ SYMBOLS = {
     "ctf_observe_stores_hinted": (C.c_int32, [_P, _P]),
     "ctf_observe_codes": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "ctf_step_observe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    "ctf_step_observe_launches": (C.c_int32, [_P, _P]),
     "ctf_action_mask": (C.c_int, [_P, _P]),
     "ctf_get_state": (C.c_int, [_P, C.c_int32, C.POINTER(CtfStateView)]),
     "ctf_set_state": (C.c_int, [_P, C.c_int32, C.POINTER(CtfStateView)]),

@@ -29,6 +29,9 @@ extern "C" hipError_t ctf_launch_export_rng(const DevCfg&, const DevPtrs&, uint3
 extern "C" hipError_t ctf_launch_rng_refill(const DevCfg&, const DevPtrs&, int, int, int, hipStream_t);
 extern "C" hipError_t ctf_launch_get_counters(const DevCfg&, const DevPtrs&, unsigned long long*, hipStream_t);
 extern "C" hipError_t ctf_launch_set_counters(const DevCfg&, const DevPtrs&, const unsigned long long*, hipStream_t);
+extern "C" int ctf_step_observe_one_launch(const DevCfg&, const uint8_t*);
+extern "C" hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, const int8_t*, float*, double*, uint8_t*, uint32_t, uint8_t*, uint16_t*,
+                                              uint32_t, uint32_t*, uint64_t, hipStream_t);
 extern "C" hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t*, int32_t*, int32_t*, hipStream_t);
 
 struct ctf_env {
@@ -43,6 +46,8 @@ struct ctf_env {
     uint8_t* hio_dev;   // the DEVICE address of that block (hipHostGetDevicePointer)
     uint8_t* hio_host;  // its host address
     int nt_override;    // CTF_OBS_NT at create: 0 / 1 force the render's store hint off / on, -1 = the rule (store_hint)
+    uint32_t* sync;     // device, ctf_sync_words(E) u32, zeroed at create: k_step_observe's generation, reader counters and flags
+    uint64_t spin_ticks;  // 10 ms of the device's wall clock: a render tile's bound on its wait in k_step_observe
 };
 
 // Layout of the ctf_host_step block (byte offsets; every segment 16-byte aligned, the observation 256-byte aligned).
@@ -126,6 +131,7 @@ static void free_all(ctf_env* h) {
     (void)hipFree((void*)h->p.init_grid); (void)hipFree((void*)h->p.meta_lut); (void)hipFree(h->p.status); (void)hipFree(h->seed_scratch);
     (void)hipFree(h->p.rngctr); (void)hipFree(h->rng_scratch); (void)hipFree(h->p.rngready); (void)hipFree(h->p.rngage);
     (void)hipFree(h->p.py_top); (void)hipFree(h->p.np_hit); (void)hipFree(h->p.np_nib);
+    (void)hipFree(h->sync);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     delete h;
 }
@@ -148,6 +154,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     h->rng_scratch = nullptr;
     h->hio_dev = nullptr;
     h->hio_host = nullptr;
+    h->sync = nullptr;
     {
         const char* ov = getenv("CTF_OBS_NT");
         h->nt_override = ov ? (atoi(ov) != 0) : -1;
@@ -157,6 +164,11 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) { free_all(h); return fail(CTF_E_HIP, "hipGetDeviceProperties failed"); }
     h->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     h->d.n_cus = d.n_cus = h->n_cus;
+    {
+        int khz = 0;  // the wall clock's rate (100 MHz on CDNA3 / CDNA4)
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) != hipSuccess || khz <= 0) khz = 100000;
+        h->spin_ticks = (uint64_t)khz * 10;
+    }
     const size_t E = (size_t)n_envs;
     const size_t vis_elems = d.log_metrics ? E * d.N * d.GS : 1, met_elems = d.log_metrics ? E * CTF_N_METRICS * d.N : 1;
 #define ALLOC(ptr, bytes)                                                                                      \
@@ -180,6 +192,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     ALLOC(h->p.meta_lut, (size_t)round_up(d.N * d.M, 16));
     ALLOC(h->p.status, 4);
     ALLOC(h->seed_scratch, E * 2 * 8);
+    ALLOC(h->sync, ctf_sync_words(n_envs) * 4);
 #undef ALLOC
     std::vector<uint8_t> g0((size_t)d.GS, 0);
     memcpy(g0.data(), cfg->init_grid, (size_t)d.GG);
@@ -189,6 +202,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     if (hipMemcpy((void*)h->p.meta_lut, lut.data(), lut.size(), hipMemcpyHostToDevice) != hipSuccess) { free_all(h); return fail(CTF_E_HIP, "device initialisation failed"); }
     hipError_t e2 = hipMemset(h->p.status, 0, 4);
     hipError_t e3 = hipMemset(h->p.rec, 0, E * d.RS);
+    if (e3 == hipSuccess) e3 = hipMemset(h->sync, 0, ctf_sync_words(n_envs) * 4);
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { free_all(h); return fail(CTF_E_HIP, "device initialisation failed"); }
     // first reset (+ _arr = [0..N-1], gridworld_ctf.py:244) and seeds 0/0
     hipError_t e4 = ctf_launch_reset(h->d, h->p, nullptr, 1, nullptr);
@@ -375,12 +389,23 @@ extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, 
     // (The ring regeneration rides at the tail of the step launch.  Running it as a launch of its own on a second stream, beside
     // the render, was built and measured in round 3: the render lost more than the step kernel gained — 189-191 M against 198 M
     // env-steps/s, profiles/r03_side_stream_ablation.md.)
+    if (ctf_step_observe_one_launch(h->d, obs)) {
+        h->d.obs_store_nt = store_hint(h);
+        HIP_TRY(ctf_launch_step_observe(h->d, h->p, actions, rw32, rw64, done, flags, obs, meta, resolve_reverse(h, reverse_mask), h->sync,
+                                        h->spin_ticks, (hipStream_t)stream));
+        return CTF_OK;
+    }
     HIP_TRY(ctf_launch_step(h->d, h->p, actions, rw32, rw64, done, flags, 1, (hipStream_t)stream));
     if (obs || meta) {
         h->d.obs_store_nt = store_hint(h);
         HIP_TRY(ctf_launch_observe(h->d, h->p, obs, meta, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
     }
     return CTF_OK;
+}
+
+extern "C" int32_t ctf_step_observe_launches(const ctf_env* h, const uint8_t* obs) {
+    if (!h) return -1;
+    return ctf_step_observe_one_launch(h->d, obs) ? 1 : 2;
 }
 
 extern "C" int ctf_action_mask(const ctf_env* h, uint8_t* mask_host) {

@@ -33,7 +33,7 @@
 #define CTF_OBS_TILE 8192  // bytes of the flat observation buffer one wave of k_observe_tiles renders (-D: profiling)
 #endif
 #ifndef CTF_OBS_TILE_WPB
-#define CTF_OBS_TILE_WPB 4  // independent one-wave tiles per block (-D: profiling)
+#define CTF_OBS_TILE_WPB 1  // independent one-wave tiles per block (-D: profiling; 4 until the occupancy cap of k_observe_tiles)
 #endif
 
 struct FastDiv {  // q = (n * m) >> s, exact for every n the kernels use (verified on the host at create)
@@ -115,4 +115,16 @@ struct DevPtrs {
 #define CTF_F_BASE_ZERO 2
 #define CTF_F_FOLDED_SHIFT 2
 #define CTF_VIS_LOG 512
+
+// k_step_observe's sync words (u32 [ctf_sync_words(E)] per handle, zeroed at create): the generation `seq` (word 0),
+// CTF_SYNC_SHARDS reader counters (one 128-byte line each) and, from word CTF_SYNC_FLAGS, one flag per step block.  In the
+// launch that finds seq = s a step block publishes flag = s + 1; every step and tile block reads seq first and then counts
+// itself on its shard; step block 0, once every reader has been counted, zeroes the shards and sets seq = s + 1 for the next
+// launch (no block of this launch can still read it).  Nothing depends on a launch argument that changes from call to call.
+#define CTF_SYNC_LINE 32
+#ifndef CTF_SYNC_SHARDS
+#define CTF_SYNC_SHARDS 256  // a power of two >= 64: 16 lines cost the single launch 20 us of its 0.3 ms (every block counts itself once)
+#endif
+#define CTF_SYNC_FLAGS (CTF_SYNC_LINE * (1 + CTF_SYNC_SHARDS))
+static inline size_t ctf_sync_words(int n_envs) { return (size_t)CTF_SYNC_FLAGS + (size_t)n_envs / 8 + 1; }  // a step block has >= 8 envs
 #define CTF_POS_MASK 0xFFFFu

@@ -422,31 +422,39 @@ __device__ __forceinline__ void tail_block(const DevCfg& cfg, const DevPtrs& p, 
     (void)n_done;
 #endif
 }
-// 16 blocks (= waves) per CU fit by LDS: the register budget is held to the matching 4 waves per SIMD (128 VGPRs)
-template <bool METRICS, int W>
-__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
-k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restrict__ rw32, double* __restrict__ rw64,
-       uint8_t* __restrict__ done_out, uint32_t flags, int n_step_blocks) {
+// ---- hand-off of a step block's envs to the render tiles of the same launch (k_step_observe).  The two usually sit on different
+// XCDs, whose L2s are not coherent: the step block stores the grids and records write-through (agent-scope stores: `sc1`), waits
+// for them (vmcnt(0)), then ONE lane stores the block's flag (agent scope); a tile polls the flag with agent-scope loads and reads
+// the envs' grid and record with agent-scope loads only (`sc1`: served past this CU's L1 from a coherent level), so no acquire
+// fence is needed.  The flags hold a generation number (StepSync), never a per-call launch argument: a captured launch replays.
+typedef __attribute__((address_space(1))) uint32_t gu32_t;
+typedef __attribute__((address_space(1))) unsigned long long gu64_t;
+__device__ __forceinline__ uint32_t ld_sc1(const uint32_t* a) {
+    return __hip_atomic_load((gu32_t*)(uint32_t*)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_sc1(uint32_t* a, uint32_t v) { __hip_atomic_store((gu32_t*)a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store_sc1_x4(void* dst, u32x4_t v) {  // 16 bytes as two 8-byte write-through stores
+    gu64_t* g = (gu64_t*)dst;
+    __hip_atomic_store(g, (unsigned long long)v.x | ((unsigned long long)v.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(g + 1, (unsigned long long)v.z | ((unsigned long long)v.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+struct StepPub {
+    uint32_t* flags;
+    uint32_t value;  // seq + 1
+};
+__device__ __forceinline__ void step_publish(const StepPub& pub, int sb, int lane) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every write-through store of the block has landed
+    if (lane == 0) st_sc1(pub.flags + sb, pub.value);
+}
+
+// The step of the EPW envs of step block sb (k_step, and the step blocks of k_step_observe).  PUBLISH (k_step_observe): the
+// grids and records leave write-through and the block's flag follows them (StepPub).
+template <bool METRICS, int W, bool PUBLISH>
+__device__ __forceinline__ void step_block(const DevCfg& cfg, const DevPtrs& p, const int8_t* __restrict__ actions, float* __restrict__ rw32,
+                                           double* __restrict__ rw64, uint8_t* __restrict__ done_out, uint32_t flags, int sb, int lane,
+                                           uint32_t* lds, const StepPub& pub) {
     constexpr int EPW = WAVE / W;  // envs per wave
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    extern __shared__ uint32_t lds[];
-    const int lane = threadIdx.x;
-#ifndef STEP_TAIL_FIRST
-#define STEP_TAIL_FIRST 0  // 1 (measured, not shipped): the ring-regenerating blocks at the HEAD of the grid instead of its tail
-#endif
-    const int n_tail_blocks = (int)gridDim.x - n_step_blocks;
-    const int sb = STEP_TAIL_FIRST ? (int)blockIdx.x - n_tail_blocks : (int)blockIdx.x;  // this step block's index
-    if (STEP_TAIL_FIRST ? sb < 0 : sb >= n_step_blocks) {
-        // ---- a TAIL block (see tail_block): these start as step blocks retire — the LDS is full until then
-        tail_block(cfg, p, STEP_TAIL_FIRST ? (int)blockIdx.x : sb - n_step_blocks, lane, lds);
-        return;
-    }
-    STEP_STAMP(0);
-#if STEP_TRACE
-    if (threadIdx.x == 0 && blockIdx.x < 8192)
-        g_step_trace[blockIdx.x][39] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
-                                       ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
-#endif
     const int g = lane / W, j = lane % W;
     const int env0 = sb * EPW;
     const int nvalid = min(EPW, cfg.n_envs - env0);
@@ -552,15 +560,18 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
             const int el = (int)fdiv((uint32_t)q, cfg.div_gq), w = (q - el * GQ) * 4;
             const uint32_t* slot = lds + el * SLW + w;
             const u32x4 v = {slot[0], slot[1], slot[2], slot[3]};
-            gdst[q] = v;
+            if (PUBLISH) store_sc1_x4(gdst + q, v);
+            else gdst[q] = v;
         }
 #pragma unroll 2
         for (int q = lane; q < nr; q += WAVE) {
             const int el = (int)fdiv((uint32_t)q, cfg.div_rq), w = (q - el * RQ) * 4;
             const uint32_t* slot = lds + el * SLW + GW + w;
             const u32x4 v = {slot[0], slot[1], slot[2], slot[3]};
-            rdst[q] = v;
+            if (PUBLISH) store_sc1_x4(rdst + q, v);
+            else rdst[q] = v;
         }
+        if (PUBLISH) step_publish(pub, sb, lane);
         if (METRICS && !(STEP_ABLATE & 32)) {
             // this step's u8 deltas are added to the i32 counters with no-return atomics (nothing to wait for); two
             // neighbouring counters share one 64-bit add (a counter never carries out of its 32 bits)
@@ -583,6 +594,32 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
         }
     }
     STEP_STAMP(4);
+}
+
+// 16 blocks (= waves) per CU fit by LDS: the register budget is held to the matching 4 waves per SIMD (128 VGPRs)
+template <bool METRICS, int W>
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restrict__ rw32, double* __restrict__ rw64,
+       uint8_t* __restrict__ done_out, uint32_t flags, int n_step_blocks) {
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x;
+#ifndef STEP_TAIL_FIRST
+#define STEP_TAIL_FIRST 0  // 1 (measured, not shipped): the ring-regenerating blocks at the HEAD of the grid instead of its tail
+#endif
+    const int n_tail_blocks = (int)gridDim.x - n_step_blocks;
+    const int sb = STEP_TAIL_FIRST ? (int)blockIdx.x - n_tail_blocks : (int)blockIdx.x;  // this step block's index
+    if (STEP_TAIL_FIRST ? sb < 0 : sb >= n_step_blocks) {
+        // ---- a TAIL block (see tail_block): these start as step blocks retire — the LDS is full until then
+        tail_block(cfg, p, STEP_TAIL_FIRST ? (int)blockIdx.x : sb - n_step_blocks, lane, lds);
+        return;
+    }
+    STEP_STAMP(0);
+#if STEP_TRACE
+    if (threadIdx.x == 0 && blockIdx.x < 8192)
+        g_step_trace[blockIdx.x][39] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
+                                       ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+#endif
+    step_block<METRICS, W, false>(cfg, p, actions, rw32, rw64, done_out, flags, sb, lane, lds, StepPub{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -609,6 +646,11 @@ __host__ __device__ inline int obs_wave_bytes(int RS, int N, int M, int obs_byte
 
 #ifndef OBS_TILES_DEFAULT
 #define OBS_TILES_DEFAULT 1  // ctf_launch_observe takes the tile render whenever it applies (CTF_OBS_TILES=0 / 1 overrides)
+#endif
+#ifndef STEP_OBSERVE_ONE_LAUNCH_DEFAULT
+// ctf_step_observe is k_step_observe only when CTF_STEP_OBSERVE_ONE_LAUNCH=1 (and the tile render applies): measured at 65 536
+// arena envs it is 9 % SLOWER than the two launches (0.325 against 0.298 ms, profiles/r06_one_launch_step_observe.md)
+#define STEP_OBSERVE_ONE_LAUNCH_DEFAULT 0
 #endif
 #define LGKM_ONLY 0xC07F  // s_waitcnt lgkmcnt(0): LDS traffic only — never drain the wave's outstanding stores
 // Profiling-only ablations (never defined in the shipped build; see tools/ablate.sh):
@@ -954,23 +996,46 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
 // Metadata rows: written by the wave whose tile holds an env's first byte.
 // Used when an env's block is a multiple of 16 bytes and >= one tile and the buffer is 16-byte aligned (ctf_launch_observe).
 #define OBS_TILE CTF_OBS_TILE
+#ifndef OBS_TILE_BLOCK_LDS
+#define OBS_TILE_BLOCK_LDS (10 * 1024)  // dynamic LDS of a k_observe_tiles block at least: 160 KiB / 10 KiB = 16 blocks (waves) per CU
+#endif
 __host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
     return OBS_TILE / 8 + RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M);
 }
 
-template <int STORE_NT>  // 1 (batches whose observations exceed the memory-side cache, ctf_derive.h): the tile's stores carry the nontemporal hint
-__global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) k_observe_tiles(DevCfg cfg, DevPtrs p, uint8_t* __restrict__ obs, uint16_t* __restrict__ meta,
-                                                       uint32_t reverse_mask, uint32_t xcd_map) {
-    extern __shared__ uint32_t lds[];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const int N = cfg.N, M = cfg.M, G = cfg.G, GG = cfg.GG, CGG = cfg.CGG, OB = cfg.obs_bytes;
-    // ---- which tile of which group of envs (uniform, 32-bit)
-    // The launch is 1-D and consecutive workgroups go to consecutive XCDs (8 of them).  Block b therefore takes logical
-    // block (b % 8) * (blocks / 8) + b / 8: every XCD writes ITS OWN contiguous eighth of the buffer front to back instead of
-    // every XCD touching every page — a constant 8 KiB-tile fill measures 6.2 instead of 5.6 TB/s that way (profiles/r02_store_bw9_xcd.txt).
-    const uint32_t b = blockIdx.x;
-    const uint32_t lb = xcd_map ? (b & 7u) * ((uint32_t)cfg.tile_nb >> 3) + (b >> 3) : b;
+// What a tile of k_step_observe waits for: the flags of the (one or two) step blocks of its envs (EPW = 1 << epw_shift envs each).
+struct TileWait {
+    const uint32_t* sync;  // the handle's sync words: seq, then (from CTF_SYNC_FLAGS) the step blocks' flags
+    int epw_shift;
+    uint64_t ticks;        // bound of the wait (wall clock): then CTF_ST_SYNC_TIMEOUT and the tile goes on
+};
+// One lane: seq and the two flags are loaded together (one round trip in the common case, the step blocks long done); then the
+// flags alone are polled until both hold seq + 1.
+__device__ __forceinline__ bool wait_flags(const TileWait& tw, int sa, int sz) {
+    const uint32_t* fa = tw.sync + CTF_SYNC_FLAGS + sa;
+    const uint32_t* fz = tw.sync + CTF_SYNC_FLAGS + sz;
+    const uint32_t seq = ld_sc1(tw.sync);
+    uint32_t a = ld_sc1(fa), z = ld_sc1(fz);
+    const uint32_t value = seq + 1u;
+    if (a == value && z == value) return true;
+    const uint64_t t0 = wall_clock64();
+    for (;;) {
+        __builtin_amdgcn_s_sleep(2);
+        if (a != value) a = ld_sc1(fa);
+        if (z != value) z = ld_sc1(fz);
+        if (a == value && z == value) return true;
+        if (wall_clock64() - t0 > tw.ticks) return false;
+    }
+}
+// the state of the envs the tile reads: with SYNC (k_step_observe) agent-scope (`sc1`) loads, see StepPub
+template <bool SYNC>
+__device__ __forceinline__ uint32_t ld_state(const uint32_t* a) { return SYNC ? ld_sc1(a) : *a; }
+
+// One tile: logical block lb (XCD map applied), wave `wave` of it; wl = the wave's LDS.  SYNC: k_step_observe's tile (TileWait).
+template <int STORE_NT, bool SYNC>
+__device__ __forceinline__ void tile_render(const DevCfg& cfg, const DevPtrs& p, uint8_t* __restrict__ obs, uint16_t* __restrict__ meta,
+                                            uint32_t reverse_mask, uint32_t lb, int wave, int lane, uint8_t* wl, const TileWait& tw) {
+    const int N = cfg.N, G = cfg.G, GG = cfg.GG, CGG = cfg.CGG, OB = cfg.obs_bytes;
     const uint32_t grp = fdiv(lb, cfg.div_tile_bx);
     const int tt = (int)(lb - grp * (uint32_t)cfg.tile_bx) * CTF_OBS_TILE_WPB + wave;
     if (tt >= cfg.tile_tpg) return;
@@ -982,7 +1047,12 @@ __global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) k_observe_tiles(DevCfg 
     const int e0 = env_base + el;
     if (e0 >= cfg.n_envs) return;
     const bool two = off0 + OBS_TILE > OB && e0 + 1 < cfg.n_envs;       // the tile runs into env e0 + 1 (obs_bytes >= tile: never further)
-    uint8_t* wl = (uint8_t*)lds + wave * tiles_wave_bytes(cfg.RS, N, M);
+    if (SYNC) {  // the step blocks of e0 (and e0 + 1) must have published this launch's state
+        if (lane == 0) {
+            if (!wait_flags(tw, e0 >> tw.epw_shift, (two ? e0 + 1 : e0) >> tw.epw_shift)) atomicOr(p.status, CTF_ST_SYNC_TIMEOUT);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no instruction: the loads below stay behind the poll)
+    }
     uint32_t* bits = (uint32_t*)wl;
     const int GW = cfg.GS / 4;
     // ---- the views (flat agent blocks) the tile intersects; the last ones may lie in env e0 + 1
@@ -995,8 +1065,8 @@ __global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) k_observe_tiles(DevCfg 
     uint32_t c0[4], c1[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {  // G <= 32: at most 256 grid dwords (uniform conditions)
-        c0[j] = (GW > WAVE * j) ? g0[min(lane + WAVE * j, GW - 1)] : 0u;
-        c1[j] = (GW > WAVE * j && two) ? g1[min(lane + WAVE * j, GW - 1)] : 0u;
+        c0[j] = (GW > WAVE * j) ? ld_state<SYNC>(g0 + min(lane + WAVE * j, GW - 1)) : 0u;
+        c1[j] = (GW > WAVE * j && two) ? ld_state<SYNC>(g1 + min(lane + WAVE * j, GW - 1)) : 0u;
     }
     uint32_t own_bit = 0xFFFFFFFFu;
     {
@@ -1004,7 +1074,9 @@ __global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) k_observe_tiles(DevCfg 
         const bool nxt = fa >= N;
         if (fa <= ia1 && !(nxt && !two)) {
             const int ik = nxt ? fa - N : fa;
-            const uint16_t rc = *(const uint16_t*)(p.rec + (size_t)(nxt ? e0 + 1 : e0) * cfg.RS + cfg.off_pos + 2 * ik);
+            const uint8_t* rp = p.rec + (size_t)(nxt ? e0 + 1 : e0) * cfg.RS + cfg.off_pos + 2 * ik;
+            const uint16_t rc = SYNC ? (uint16_t)(ld_sc1((const uint32_t*)((uintptr_t)rp & ~(uintptr_t)3)) >> (8 * ((uintptr_t)rp & 2)))
+                                     : *(const uint16_t*)rp;
             const int r = (int)(int8_t)(rc & 0xFFu), c = (int)(int8_t)(rc >> 8);
             const int cell = ((reverse_mask >> ik) & 1u) ? flip_cell(cfg, r * G + c, r, c) : r * G + c;
             own_bit = (uint32_t)((nxt ? OB : 0) + ik * CGG - off0 + cell);
@@ -1091,11 +1163,95 @@ __global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) k_observe_tiles(DevCfg 
         uint8_t* srec = wl + OBS_TILE / 8;
         uint16_t* mv = (uint16_t*)(srec + cfg.RS);
         uint16_t* mstage = (uint16_t*)(srec + cfg.RS + OBS_MV_BYTES);
-        const uint32_t recw = ((const uint32_t*)(p.rec + (size_t)em * cfg.RS))[min(lane, cfg.RS / 4 - 1)];
+        const uint32_t recw = ld_state<SYNC>((const uint32_t*)(p.rec + (size_t)em * cfg.RS) + min(lane, cfg.RS / 4 - 1));
         if (lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
         const ObsSlots none = {{0u, 0u, 0u, 0u}};
         obs_build_env(cfg, p, em, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, none, reverse_mask, lane, false, meta);
     }
+}
+
+template <int STORE_NT>  // 1 (batches whose observations exceed the memory-side cache, ctf_derive.h): the tile's stores carry the nontemporal hint
+__global__ void __launch_bounds__(CTF_OBS_TILE_WPB * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_observe_tiles(DevCfg cfg, DevPtrs p, uint8_t* __restrict__ obs, uint16_t* __restrict__ meta,
+                                                       uint32_t reverse_mask, uint32_t xcd_map) {
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    // ---- which tile of which group of envs (uniform, 32-bit)
+    // The launch is 1-D and consecutive workgroups go to consecutive XCDs (8 of them).  Block b therefore takes logical
+    // block (b % 8) * (blocks / 8) + b / 8: every XCD writes ITS OWN contiguous eighth of the buffer front to back instead of
+    // every XCD touching every page — a constant 8 KiB-tile fill measures 6.2 instead of 5.6 TB/s that way (profiles/r02_store_bw9_xcd.txt).
+    const uint32_t b = blockIdx.x;
+    const uint32_t lb = xcd_map ? (b & 7u) * ((uint32_t)cfg.tile_nb >> 3) + (b >> 3) : b;
+    tile_render<STORE_NT, false>(cfg, p, obs, meta, reverse_mask, lb, wave, lane, (uint8_t*)lds + wave * tiles_wave_bytes(cfg.RS, cfg.N, cfg.M),
+                                 TileWait{});
+}
+
+// ------------------------------------------------------------------------------------------------
+// step_observe — ONE launch of one-wave blocks: [step blocks | ring-regenerating tail blocks | render tiles]
+// ------------------------------------------------------------------------------------------------
+// ctf_step followed by ctf_observe's tile render, without the kernel boundary between them: the render no longer waits for the
+// slowest of the step's waves and its tail (p50 43.8 / max 62 us, tail to 79 us: profiles/r03_kstep_phase_trace.txt) with most
+// CUs idle.  A tile waits only for the flags of the (one or two) step blocks whose envs it renders (StepPub / TileWait); the
+// blocks it waits for have lower indices, so under the in-order dispatch of a 1-D grid they are resident before it is (the
+// wait is bounded all the same: CTF_ST_SYNC_TIMEOUT).  The tail blocks sit between the two so that their ring regeneration
+// overlaps the render instead of trailing it.  One block shape for all three roles: one wave, the step's 128-VGPR budget
+// (4 waves per SIMD) and the step's LDS; tile t takes the render's tile (t % 8) * (T / 8) + t / 8 (the XCD-contiguous walk of
+// k_observe_tiles: the tiles start at a multiple of 8 blocks).  Results are those of k_step + k_observe_tiles, bit for bit.
+// Measured (8_arena, 65 536 envs, in one process on shared buffers): 0.325 ms against 0.298 for the two launches.  Without any
+// of the hand-off (no count, no waits, plain loads and stores: wrong results, timing only) the same shape takes 0.284: the
+// generation's reader count costs ≈ 20 us (at the start or at the end of a block, over 16 … 1 024 counter lines alike), the
+// waits and write-through accesses ≈ 15 more (profiles/r06_one_launch_step_observe.md).  Hence opt-in only.
+template <bool METRICS, int W, int STORE_NT>
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_step_observe(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restrict__ rw32, double* __restrict__ rw64,
+               uint8_t* __restrict__ done_out, uint32_t flags, uint8_t* __restrict__ obs, uint16_t* __restrict__ meta,
+               uint32_t reverse_mask, uint32_t xcd_map, uint32_t* __restrict__ sync, int n_step, int n_tail, int tile0,
+               uint64_t spin_ticks) {
+    constexpr int EPW = WAVE / W;
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x;
+    const int b = (int)blockIdx.x;
+    if (b >= n_step && b < tile0) {
+        if (b < n_step + n_tail) tail_block(cfg, p, b - n_step, lane, lds);  // (the rest pads the tiles' start to a multiple of 8)
+        return;
+    }
+    // Every step and tile block counts itself on a shard once it has read seq — as its LAST instruction: an atomic is counted by
+    // vmcnt, so one issued before the block's own loads would put its device-scope round trip in front of their first wait
+    // (measured: 20 us of the 0.3 ms launch; sharding the count over 16 ... 1024 lines did not help).
+    gu32_t* shard = (gu32_t*)(sync + CTF_SYNC_LINE * (1 + (b & (CTF_SYNC_SHARDS - 1))));
+    if (b < n_step) {
+        const uint32_t seq = __builtin_amdgcn_readfirstlane(ld_sc1(sync));
+        step_block<METRICS, W, true>(cfg, p, actions, rw32, rw64, done_out, flags, b, lane, lds, StepPub{sync + CTF_SYNC_FLAGS, seq + 1u});
+        if (b == 0) {
+            // once every reader of seq has been counted (itself included): zero the counters and move to the next generation
+            const uint32_t readers = (uint32_t)n_step + (gridDim.x - (uint32_t)tile0);
+            if (lane == 0) __hip_atomic_fetch_add(shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t t0 = wall_clock64();
+            for (;;) {
+                __builtin_amdgcn_s_sleep(32);
+                uint32_t n = 0;
+#pragma unroll
+                for (int k = 0; k < CTF_SYNC_SHARDS / WAVE; k++) n += ld_sc1(sync + CTF_SYNC_LINE * (1 + lane + WAVE * k));
+#pragma unroll
+                for (int o = WAVE / 2; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o, WAVE);
+                if (__builtin_amdgcn_readfirstlane(n) == readers) break;
+                if (wall_clock64() - t0 > 20 * spin_ticks) {  // (blocks not scheduled in index order: see CTF_ST_SYNC_TIMEOUT)
+                    if (lane == 0) atomicOr(p.status, CTF_ST_SYNC_TIMEOUT);
+                    break;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CTF_SYNC_SHARDS / WAVE; k++) st_sc1(sync + CTF_SYNC_LINE * (1 + lane + WAVE * k), 0u);
+            if (lane == 0) st_sc1(sync, seq + 1u);
+            return;
+        }
+    } else {
+        const uint32_t T = gridDim.x - (uint32_t)tile0, t = (uint32_t)(b - tile0);  // T: a multiple of 8
+        const uint32_t lt = xcd_map ? (t & 7u) * (T >> 3) + (t >> 3) : t;
+        tile_render<STORE_NT, true>(cfg, p, obs, meta, reverse_mask, lt / CTF_OBS_TILE_WPB, (int)(lt % CTF_OBS_TILE_WPB), lane, (uint8_t*)lds,
+                                    TileWait{sync, __builtin_ctz(EPW), spin_ticks});
+    }
+    if (lane == 0) __hip_atomic_fetch_add(shard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1393,6 +1549,38 @@ extern "C" hipError_t ctf_launch_step(const DevCfg& cfg, const DevPtrs& p, const
     else launch_step_m<false>(w, cfg, p, actions, rw32, rw64, done, flags, tail, st);
     return hipGetLastError();
 }
+// ---- k_step_observe (the launch's shape: see the kernel)
+template <bool METRICS, int W>
+static void launch_step_observe_w(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64, uint8_t* done,
+                                  uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, uint32_t* sync,
+                                  uint64_t spin_ticks, hipStream_t st) {
+    constexpr int EPW = WAVE / W;
+    const int nstep = (cfg.n_envs + EPW - 1) / EPW;
+    const int ntail = cfg.rng_refill_every ? (2 * cfg.n_envs + STEP_TAIL_PAIRS - 1) / STEP_TAIL_PAIRS : 0;
+    const int tile0 = (nstep + ntail + 7) / 8 * 8;
+    const int ntiles = cfg.tile_nb * CTF_OBS_TILE_WPB;
+    size_t sh = (size_t)EPW * step_slot_bytes(cfg.GS, cfg.RS, cfg.N, METRICS);
+    if (ntail && sh < 2 * CTF_MT_N * 4) sh = 2 * CTF_MT_N * 4;
+    if (sh < (size_t)tiles_wave_bytes(cfg.RS, cfg.N, cfg.M)) sh = (size_t)tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
+    const char* xenv = getenv("CTF_OBS_XCD");  // 0: launch-order tiles (profiling); default: XCD-contiguous
+    const uint32_t xcd_map = xenv ? (atoi(xenv) != 0) : 1u;
+    const dim3 grid((unsigned)(tile0 + ntiles)), block(WAVE);
+    if (cfg.obs_store_nt)
+        hipLaunchKernelGGL((k_step_observe<METRICS, W, 1>), grid, block, sh, st, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask,
+                           xcd_map, sync, nstep, ntail, tile0, spin_ticks);
+    else
+        hipLaunchKernelGGL((k_step_observe<METRICS, W, 0>), grid, block, sh, st, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask,
+                           xcd_map, sync, nstep, ntail, tile0, spin_ticks);
+}
+template <bool METRICS>
+static void launch_step_observe_m(int w, const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64, uint8_t* done,
+                                  uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, uint32_t* sync, uint64_t spin_ticks,
+                                  hipStream_t st) {
+    if (w <= 1) launch_step_observe_w<METRICS, 1>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    else if (w == 2) launch_step_observe_w<METRICS, 2>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    else if (w == 4) launch_step_observe_w<METRICS, 4>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    else launch_step_observe_w<METRICS, 8>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+}
 extern "C" int ctf_step_blocks(const DevCfg& cfg) { return (cfg.n_envs + WAVE / step_lanes(cfg) - 1) / (WAVE / step_lanes(cfg)); }
 #if STEP_TRACE
 // what the runtime thinks fits: blocks of k_step<true, 4> per CU at `lds` bytes of dynamic LDS, and the device's LDS per CU
@@ -1419,6 +1607,20 @@ extern "C" int ctf_observe_uses_tiles(const DevCfg& cfg, const uint8_t* obs) {
     const char* tenv = getenv("CTF_OBS_TILES");  // 0 / 1: never / whenever possible (tests, profiling)
     return obs && observe_align(cfg, obs) == 16 && cfg.tile_k > 0 && (tenv ? atoi(tenv) != 0 : OBS_TILES_DEFAULT);
 }
+// the one rule by which ctf_step_observe is one launch (1: k_step_observe) or two (0): where the tile render applies and it is asked for
+extern "C" int ctf_step_observe_one_launch(const DevCfg& cfg, const uint8_t* obs) {
+    const char* env = getenv("CTF_STEP_OBSERVE_ONE_LAUNCH");  // 0 / 1: never / whenever possible (tests, profiling)
+    return ctf_observe_uses_tiles(cfg, obs) && (env ? atoi(env) != 0 : STEP_OBSERVE_ONE_LAUNCH_DEFAULT);
+}
+// sync: the handle's sync words (ctf_sync_words); spin_ticks: a tile's bound on its wait, in wall-clock ticks
+extern "C" hipError_t ctf_launch_step_observe(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64,
+                                              uint8_t* done, uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask,
+                                              uint32_t* sync, uint64_t spin_ticks, hipStream_t st) {
+    const int w = step_lanes(cfg);
+    if (cfg.log_metrics) launch_step_observe_m<true>(w, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    else launch_step_observe_m<false>(w, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    return hipGetLastError();
+}
 extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask,
                                          int n_cus, hipStream_t st) {
     const int align = observe_align(cfg, obs);
@@ -1426,7 +1628,12 @@ extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, ui
     if (tiles) {
         // one wave per tile, 4 independent waves per block; tile_bx blocks per group of tile_k envs (whose blocks fill tile_tpg tiles)
         const int wpb = CTF_OBS_TILE_WPB;
-        const size_t sh = (size_t)wpb * tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
+        size_t sh = (size_t)wpb * tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
+        // At most 16 tile waves per CU, by the block's LDS (160 KiB per CU): fewer store streams in flight write the buffer
+        // faster.  In one process on one buffer (8_arena, 65 536 envs) the render took 0.2353 ms this way, 0.2443 ms as one-wave
+        // blocks without the cap and 0.2472 ms as the earlier blocks of 4 tiles; step + render 0.2790 / 0.2932 / 0.2980 ms
+        // (profiles/r06_render_occupancy_cap.txt).
+        if (sh < OBS_TILE_BLOCK_LDS) sh = OBS_TILE_BLOCK_LDS;
         const char* xenv = getenv("CTF_OBS_XCD");  // 0: launch-order tiles (profiling); default: XCD-contiguous
         const uint32_t xcd_map = xenv ? (atoi(xenv) != 0) : 1u;
         if (cfg.obs_store_nt) hipLaunchKernelGGL(k_observe_tiles<1>, dim3((unsigned)cfg.tile_nb), dim3(wpb * WAVE), sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);

@@ -312,6 +312,10 @@ class VecGridworldCtf:
         """Which kernel ``observe`` launches for this object's buffer: "k_observe_tiles" or "k_observe" (the library's own rule)."""
         return "k_observe_tiles" if self._lib.ctf_observe_kernel(self._h, C.c_void_p(self.obs.data_ptr())) == 1 else "k_observe"
 
+    def step_observe_launches(self):
+        """Launches ``step_observe`` makes into this object's buffer: 1 (k_step_observe) or 2 (step, then observe)."""
+        return int(self._lib.ctf_step_observe_launches(self._h, C.c_void_p(self.obs.data_ptr())))
+
     def observe_stores(self):
         """"nontemporal" when ``observe`` streams this object's buffer past the caches (the tile kernel on a batch whose observations
         exceed 320 MB), else "plain"."""
