@@ -53,6 +53,8 @@ extern "C" {
                                   followed further (a run of > 500 rejected draws: does not happen)                  */
 #define CTF_ST_SYNC_TIMEOUT 16u /* ctf_step_observe's single launch: a render tile waited longer than its bound (10 ms) for
                                    the step of its envs and went on (the launch's blocks did not run in index order)  */
+#define CTF_ST_BAD_SNAPSHOT 32u /* ctf_load_states: a record's header or destination index was wrong; that env is untouched
+                                   (ctf_save_states: a source index outside [0, E); that record's header is left invalid)      */
 
 /* ctf_config.rng_mode */
 #define CTF_RNG_MT19937 0 /* the reference's two MT19937 generators, bit for bit (default)                          */
@@ -282,6 +284,27 @@ int ctf_host_step(ctf_env* env, const int8_t* actions_host, const uint32_t* py_m
  *   captures_dev  int32 [E][2]     metrics['team_flag_captures'] or NULL
  *   steps_dev     int32 [E]        env_step_count or NULL */
 int ctf_export_counters(ctf_env* env, int32_t* metrics_dev, int32_t* captures_dev, int32_t* steps_dev, void* stream);
+
+/* Batched snapshot, restore and clone of whole env states on the device (ctf_snapshot.h has the layout).
+ * One env's state is one opaque RECORD of S = ctf_snapshot_bytes(env) bytes (a multiple of 256; it depends on the config only):
+ * a 64-byte header (magic 'CTFS', layout version 1, the handle's config fingerprint) and the env's device form copied as it is —
+ * record, grid, both streams' rings and digests with their positions, ready flags and ages, the counter-mode stream indices, and
+ * with log_metrics the counters, the visitation base maps and the env's 512-entry visitation log.  Nothing is converted, so a
+ * restored env continues bit for bit as the saved one would have.  Observations are not part of the state.
+ * Records are valid across handles and processes whose fingerprints are equal, for the same layout version; a library version
+ * that changes the layout version does not read older records.  The FINGERPRINT is a 64-bit FNV-1a over every rule and constant
+ * of the config, the init grid, N, G, C, the strides of the device form, rng_mode and log_metrics — not n_envs, the device, the
+ * seeds or the CTF_* environment switches: two handles built from the same kwargs agree.
+ * Both calls are stream-ordered kernel launches (no synchronisation, no allocation) and can be captured into a hipGraph.  Buffers
+ * are DEVICE pointers, 16-byte aligned; the index lists are DEVICE int32 arrays of n entries. */
+int64_t ctf_snapshot_bytes(const ctf_env* env);        /* S: bytes of one env's record (multiple of 256) */
+uint64_t ctf_snapshot_fingerprint(const ctf_env* env);
+/* dst_dev[k] = record of env src_idx_dev[k], k < n.  src_idx_dev NULL = envs 0..n-1 (n <= E).  Repeats allowed. */
+int ctf_save_states(ctf_env* env, const int32_t* src_idx_dev, int32_t n, uint8_t* dst_dev, void* stream);
+/* env dst_idx_dev[k] := record src_dev[k], k < n <= E.  dst_idx_dev NULL = envs 0..n-1.  Indices must be distinct
+ * (repeats: undefined).  A record whose header does not match this handle, or an index outside [0, E), writes nothing for that
+ * record and raises CTF_ST_BAD_SNAPSHOT.  Observations are not part of the state: call ctf_observe afterwards. */
+int ctf_load_states(ctf_env* env, const uint8_t* src_dev, const int32_t* dst_idx_dev, int32_t n, void* stream);
 
 /* Sticky status bits raised by any env since the last call (synchronises `stream`, clears them). */
 int ctf_status(ctf_env* env, uint32_t* out_bits, void* stream);

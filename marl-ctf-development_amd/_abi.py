@@ -20,6 +20,7 @@ ST_NO_RESPAWN = 2
 ST_SPAWN_EDGE = 4
 ST_RNG_OVERRUN = 8
 ST_SYNC_TIMEOUT = 16
+ST_BAD_SNAPSHOT = 32
 STEP_AUTO_RESET = 1
 RNG_MT19937 = 0
 RNG_COUNTER = 1
@@ -135,6 +136,10 @@ SYMBOLS = {
     "ctf_set_state": (C.c_int, [_P, C.c_int32, C.POINTER(CtfStateView)]),
     "ctf_host_step": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
                                 C.POINTER(CtfStateView), _P, _P, _P, _P, _P]),
+    "ctf_snapshot_bytes": (C.c_int64, [_P]),
+    "ctf_snapshot_fingerprint": (C.c_uint64, [_P]),
+    "ctf_save_states": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "ctf_load_states": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ctf_export_counters": (C.c_int, [_P, _P, _P, _P, _P]),
     "ctf_status": (C.c_int, [_P, C.POINTER(C.c_uint32), _P]),
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ctf_device.h"
+#include "ctf_snapshot.h"
 
 extern "C" hipError_t ctf_launch_seed(const DevCfg&, const DevPtrs&, const uint64_t*, const uint64_t*, hipStream_t);
 extern "C" hipError_t ctf_launch_reset(const DevCfg&, const DevPtrs&, const uint8_t*, int, hipStream_t);
@@ -33,6 +34,8 @@ extern "C" int ctf_step_observe_one_launch(const DevCfg&, const uint8_t*);
 extern "C" hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, const int8_t*, float*, double*, uint8_t*, uint32_t, uint8_t*, uint16_t*,
                                               uint32_t, uint32_t*, uint64_t, hipStream_t);
 extern "C" hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t*, int32_t*, int32_t*, hipStream_t);
+extern "C" hipError_t ctf_launch_save_states(const SnapLayout&, const int32_t*, int, uint8_t*, hipStream_t);         // ctf_snapshot.hip
+extern "C" hipError_t ctf_launch_load_states(const SnapLayout&, const uint8_t*, const int32_t*, int, hipStream_t);
 
 struct ctf_env {
     ctf_config cfg;
@@ -48,6 +51,7 @@ struct ctf_env {
     int nt_override;    // CTF_OBS_NT at create: 0 / 1 force the render's store hint off / on, -1 = the rule (store_hint)
     uint32_t* sync;     // device, ctf_sync_words(E) u32, zeroed at create: k_step_observe's generation, reader counters and flags
     uint64_t spin_ticks;  // 10 ms of the device's wall clock: a render tile's bound on its wait in k_step_observe
+    uint64_t fingerprint;  // of the config (ctf_snapshot.h): which handles' snapshot records this one reads
 };
 
 // Layout of the ctf_host_step block (byte offsets; every segment 16-byte aligned, the observation 256-byte aligned).
@@ -160,6 +164,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
         h->nt_override = ov ? (atoi(ov) != 0) : -1;
     }
     h->cfg = *cfg; h->d = d; h->device = device_id;
+    h->fingerprint = snap_fingerprint(cfg, d);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) { free_all(h); return fail(CTF_E_HIP, "hipGetDeviceProperties failed"); }
     h->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -656,6 +661,33 @@ extern "C" int ctf_export_counters(ctf_env* h, int32_t* metrics_dev, int32_t* ca
     if (!metrics_dev && !captures_dev && !steps_dev) return CTF_OK;
     DeviceGuard guard(h->device);
     HIP_TRY(ctf_launch_export_counters(h->d, h->p, metrics_dev, captures_dev, steps_dev, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+// ---- snapshot records (ctf_snapshot.h / ctf_snapshot.hip) ----------------------------------------------------------------------
+extern "C" int64_t ctf_snapshot_bytes(const ctf_env* h) { return h ? snap_layout(h->d, h->p, h->fingerprint).bytes : 0; }
+extern "C" uint64_t ctf_snapshot_fingerprint(const ctf_env* h) { return h ? h->fingerprint : 0; }
+
+static int snap_args(const ctf_env* h, int32_t n, const void* buf, const char* what) {
+    if (!h || !buf) return fail(CTF_E_INVALID, "%s: null argument", what);
+    if (n < 0) return fail(CTF_E_INVALID, "%s: n = %d", what, n);
+    if ((uintptr_t)buf % 16) return fail(CTF_E_INVALID, "%s: the record buffer must be 16-byte aligned", what);
+    return CTF_OK;
+}
+
+extern "C" int ctf_save_states(ctf_env* h, const int32_t* src_idx, int32_t n, uint8_t* dst, void* stream) {
+    if (int rc = snap_args(h, n, dst, "ctf_save_states")) return rc;
+    if (!src_idx && n > h->d.n_envs) return fail(CTF_E_RANGE, "ctf_save_states: n = %d > %d envs", n, h->d.n_envs);
+    DeviceGuard guard(h->device);
+    HIP_TRY(ctf_launch_save_states(snap_layout(h->d, h->p, h->fingerprint), src_idx, n, dst, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+extern "C" int ctf_load_states(ctf_env* h, const uint8_t* src, const int32_t* dst_idx, int32_t n, void* stream) {
+    if (int rc = snap_args(h, n, src, "ctf_load_states")) return rc;
+    if (n > h->d.n_envs) return fail(CTF_E_RANGE, "ctf_load_states: n = %d > %d envs", n, h->d.n_envs);
+    DeviceGuard guard(h->device);
+    HIP_TRY(ctf_launch_load_states(snap_layout(h->d, h->p, h->fingerprint), src, dst_idx, n, (hipStream_t)stream));
     return CTF_OK;
 }
 

@@ -390,6 +390,95 @@ class VecGridworldCtf:
         _abi.check(self._lib.ctf_action_mask(self._h, m.ctypes.data_as(C.c_void_p)), self._lib)
         return m
 
+    # -- snapshots: whole env states as opaque device records (include/ctf_env.h, ctf_save_states) ---------------------------
+    # Records are valid for any handle of the same ``fingerprint`` (same kwargs, rng_mode and log_metrics; any n_envs, seeds or
+    # device), across processes (torch.save / torch.load of the buffer).  Not for the drop-in ``GridworldCtf``: it caches the
+    # generator states of its env (_py_last / _np_last), so ``load_states`` on a facade's ``_vec`` is unsupported.
+    @property
+    def snapshot_bytes(self):
+        """S: bytes of one env's record (a multiple of 256; depends on the config only)."""
+        return int(self._lib.ctf_snapshot_bytes(self._h))
+
+    @property
+    def fingerprint(self):
+        """64-bit fingerprint of the config: records move between handles whose fingerprints are equal."""
+        return int(self._lib.ctf_snapshot_fingerprint(self._h))
+
+    def _index_list(self, idx, what, check):
+        """idx (None, int tensor, numpy array or sequence) -> (int32 tensor on the device or None, n).  Host inputs are checked
+        for range here (free); device tensors only when ``check`` (one synchronisation)."""
+        torch = _torch()
+        if idx is None:
+            return None, self.n_envs
+        if isinstance(idx, torch.Tensor):
+            if idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool or idx.dim() != 1:
+                raise ValueError(f"{what}: expected a 1-D integer index tensor")
+            host = not idx.is_cuda
+        else:
+            arr = np.asarray(idx)
+            if arr.ndim != 1 or not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError(f"{what}: expected a 1-D integer index array")
+            idx, host = torch.from_numpy(np.ascontiguousarray(arr)), True
+        if host or check:
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n_envs):
+                raise ValueError(f"{what}: an index is outside [0, {self.n_envs})")
+        elif idx.device != self.device:
+            raise ValueError(f"{what}: index tensor on {idx.device}, the envs are on {self.device}")
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        return idx, int(idx.numel())
+
+    def _records(self, buf, n, what):
+        torch = _torch()
+        S = self.snapshot_bytes
+        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.uint8 and buf.is_cuda and buf.device == self.device):
+            raise ValueError(f"{what}: expected a uint8 tensor on {self.device}")
+        if buf.dim() != 2 or buf.shape[1] != S or (n is not None and buf.shape[0] != n):
+            raise ValueError(f"{what}: expected shape [{'n' if n is None else n}, {S}], got {list(buf.shape)}")
+        if not buf.is_contiguous() or buf.data_ptr() % 16:
+            raise ValueError(f"{what}: the record buffer must be contiguous and 16-byte aligned")
+        return C.c_void_p(buf.data_ptr())
+
+    def save_states(self, idx=None, out=None):
+        """Records of envs ``idx`` (None: all) -> uint8 [n, snapshot_bytes] on the env's device (``out`` if given).  Stream-ordered:
+        no synchronisation; repeats allowed."""
+        torch = _torch()
+        ix, n = self._index_list(idx, "save_states", check=False)
+        if out is None:
+            out = torch.empty((n, self.snapshot_bytes), dtype=torch.uint8, device=self.device)
+        ptr = self._records(out, n, "save_states")
+        _abi.check(self._lib.ctf_save_states(self._h, None if ix is None else C.c_void_p(ix.data_ptr()), n, ptr, self._stream()),
+                   self._lib)
+        return out
+
+    def load_states(self, buf, idx=None, check=True):
+        """Env ``idx[k]`` := record ``buf[k]`` (idx None: envs 0..n-1).  Observations are not state: call ``observe`` afterwards.
+        ``check`` rejects repeated or out-of-range indices (one synchronisation); ``check=False`` skips that (graph capture) —
+        the kernel still refuses a record whose header does not match this handle, or an index outside [0, E): that env is left
+        as it was and ``status()`` shows ST_BAD_SNAPSHOT."""
+        torch = _torch()
+        n = buf.shape[0] if isinstance(buf, torch.Tensor) and buf.dim() == 2 else None
+        ptr = self._records(buf, n, "load_states")
+        n = int(buf.shape[0])
+        if n > self.n_envs:
+            raise ValueError(f"load_states: {n} records for {self.n_envs} envs")
+        ix, m = (None, n) if idx is None else self._index_list(idx, "load_states", check)
+        if m != n:
+            raise ValueError(f"load_states: {n} records but {m} indices")
+        if check and ix is not None and torch.unique(ix).numel() != n:
+            raise ValueError("load_states: repeated indices")
+        _abi.check(self._lib.ctf_load_states(self._h, ptr, None if ix is None else C.c_void_p(ix.data_ptr()), n, self._stream()),
+                   self._lib)
+
+    def clone_envs(self, src_idx, dst_idx, check=True):
+        """Env ``dst_idx[k]`` := the state of env ``src_idx[k]`` (through a scratch buffer this object owns, so the two sets may
+        overlap: a permutation in place is legal).  Stream-ordered apart from ``check`` (see ``load_states``)."""
+        src, n = self._index_list(src_idx, "clone_envs", check)
+        scratch = getattr(self, "_clone_scratch", None)
+        if scratch is None or scratch.shape[0] < n:
+            scratch = self._clone_scratch = _torch().empty((n, self.snapshot_bytes), dtype=_torch().uint8, device=self.device)
+        recs = self.save_states(src, out=scratch[:n])
+        self.load_states(recs, dst_idx, check=check)
+
     # -- host views ---------------------------------------------------------------------------
     def get_state(self, env_index):
         v = _abi.CtfStateView()
