@@ -13,7 +13,7 @@
  *     the library never allocates or frees I/O buffers;
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
- *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe and ctf_reset are kernel launches and nothing else (no
+ *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset and ctf_harvest_episodes are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -55,6 +55,7 @@ extern "C" {
                                    the step of its envs and went on (the launch's blocks did not run in index order)  */
 #define CTF_ST_BAD_SNAPSHOT 32u /* ctf_load_states: a record's header or destination index was wrong; that env is untouched
                                    (ctf_save_states: a source index outside [0, E); that record's header is left invalid)      */
+#define CTF_ST_BAD_GROUP 64u    /* ctf_harvest_episodes: a group id outside [0, n_groups); that env is skipped                 */
 
 /* ctf_config.rng_mode */
 #define CTF_RNG_MT19937 0 /* the reference's two MT19937 generators, bit for bit (default)                          */
@@ -305,6 +306,29 @@ int ctf_save_states(ctf_env* env, const int32_t* src_idx_dev, int32_t n, uint8_t
  * (repeats: undefined).  A record whose header does not match this handle, or an index outside [0, E), writes nothing for that
  * record and raises CTF_ST_BAD_SNAPSHOT.  Observations are not part of the state: call ctf_observe afterwards. */
 int ctf_load_states(ctf_env* env, const uint8_t* src_dev, const int32_t* dst_idx_dev, int32_t n, void* stream);
+
+/* Harvest of finished episodes into per-group results, on the device (ctf_harvest.h has the row; the batched form of what
+ * utils.duel's result sign, utils.py:562-569, and MetricsLogger.harvest_metrics, metrics_logger.py:137-159, read from one env).
+ * acc_dev is a caller-owned table int64 [n_groups][H], H = ctf_harvest_words(env) = 8 + 13 * N, that the call ADDS to (the caller
+ * zeroes it).  Row g sums over the taken envs e with group_dev[e] == g:
+ *   [0] episodes   [1] team-0 wins   [2] draws   [3] team-1 wins (the sign of team_flag_captures[0] - [1])
+ *   [4] [5] team_flag_captures of team 0 / 1   [6] env_step_count   [7] reserved (never written)
+ *   [8 + m * N + i] agent-level counter m (CTF_M_* order) of agent i; with log_metrics == 0 these words are left untouched and the
+ *   first seven are still counted.
+ * Which envs are taken: those whose episode ended in the most recent step — `done` set AND env_step_count == GAME_STEPS.  That
+ * holds for exactly one step per episode in both stepping modes: with CTF_STEP_AUTO_RESET the next step resets the env (count 1),
+ * without it the env runs on past GAME_STEPS (`done` stays set, the count moves on).  So ONE call after EVERY step neither drops
+ * nor double-counts an episode.  Two calls without a step in between count the same episodes twice; two steps without a call in
+ * between lose the episodes of the envs that auto-reset in the second one.  CTF_HARVEST_ALL takes every env as it stands, ended
+ * or not: the cut of a truncated duel (utils.py:559, step_count > max_steps).
+ *   group_dev     int32 [E], or NULL: every env is group 0.  An id outside [0, n_groups) skips that env and raises CTF_ST_BAD_GROUP
+ *   env_mask_dev  uint8 [E], or NULL: only envs whose byte is non-zero are looked at
+ * One kernel launch and nothing else (capturable behind ctf_step_observe); env state is only read; the sums are integer sums, so
+ * the table does not depend on the order in which envs are added.  acc_dev must be 8-byte aligned. */
+#define CTF_HARVEST_ALL 1u
+int32_t ctf_harvest_words(const ctf_env* env);
+int ctf_harvest_episodes(ctf_env* env, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
+                         int64_t* acc_dev, void* stream);
 
 /* Sticky status bits raised by any env since the last call (synchronises `stream`, clears them). */
 int ctf_status(ctf_env* env, uint32_t* out_bits, void* stream);

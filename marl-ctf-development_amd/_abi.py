@@ -21,7 +21,10 @@ ST_SPAWN_EDGE = 4
 ST_RNG_OVERRUN = 8
 ST_SYNC_TIMEOUT = 16
 ST_BAD_SNAPSHOT = 32
+ST_BAD_GROUP = 64
 STEP_AUTO_RESET = 1
+HARVEST_ALL = 1
+HARVEST_HEAD = 8  # words of a harvest row before the counters (include/ctf_env.h, ctf_harvest_episodes)
 RNG_MT19937 = 0
 RNG_COUNTER = 1
 REVERSE_DEFAULT = 0xFFFFFFFF
@@ -140,6 +143,8 @@ SYMBOLS = {
     "ctf_snapshot_fingerprint": (C.c_uint64, [_P]),
     "ctf_save_states": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "ctf_load_states": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "ctf_harvest_words": (C.c_int32, [_P]),
+    "ctf_harvest_episodes": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P]),
     "ctf_export_counters": (C.c_int, [_P, _P, _P, _P, _P]),
     "ctf_status": (C.c_int, [_P, C.POINTER(C.c_uint32), _P]),
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ctf_device.h"
+#include "ctf_harvest.h"
 #include "ctf_snapshot.h"
 
 extern "C" hipError_t ctf_launch_seed(const DevCfg&, const DevPtrs&, const uint64_t*, const uint64_t*, hipStream_t);
@@ -36,6 +37,7 @@ extern "C" hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, con
 extern "C" hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t*, int32_t*, int32_t*, hipStream_t);
 extern "C" hipError_t ctf_launch_save_states(const SnapLayout&, const int32_t*, int, uint8_t*, hipStream_t);         // ctf_snapshot.hip
 extern "C" hipError_t ctf_launch_load_states(const SnapLayout&, const uint8_t*, const int32_t*, int, hipStream_t);
+extern "C" hipError_t ctf_launch_harvest(const HarvestArgs&, const int32_t*, int, const uint8_t*, uint32_t, int64_t*, hipStream_t);  // ctf_harvest.hip
 
 struct ctf_env {
     ctf_config cfg;
@@ -688,6 +690,21 @@ extern "C" int ctf_load_states(ctf_env* h, const uint8_t* src, const int32_t* ds
     if (n > h->d.n_envs) return fail(CTF_E_RANGE, "ctf_load_states: n = %d > %d envs", n, h->d.n_envs);
     DeviceGuard guard(h->device);
     HIP_TRY(ctf_launch_load_states(snap_layout(h->d, h->p, h->fingerprint), src, dst_idx, n, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+// ---- episode harvest (ctf_harvest.h / ctf_harvest.hip) -------------------------------------------------------------------------
+extern "C" int32_t ctf_harvest_words(const ctf_env* h) { return h ? harvest_words(h->d.N) : 0; }
+
+extern "C" int ctf_harvest_episodes(ctf_env* h, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
+                                    int64_t* acc_dev, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_harvest_episodes: null handle");
+    if (n_groups < 1) return fail(CTF_E_INVALID, "ctf_harvest_episodes: n_groups = %d", n_groups);
+    if (!acc_dev) return fail(CTF_E_INVALID, "ctf_harvest_episodes: null table");
+    if ((uintptr_t)acc_dev % 8) return fail(CTF_E_INVALID, "ctf_harvest_episodes: the table must be 8-byte aligned");
+    if (flags & ~CTF_HARVEST_ALL) return fail(CTF_E_INVALID, "ctf_harvest_episodes: unknown flags 0x%x", flags);
+    DeviceGuard guard(h->device);
+    HIP_TRY(ctf_launch_harvest(harvest_args(h->d, h->p), group_dev, n_groups, env_mask_dev, flags, acc_dev, (hipStream_t)stream));
     return CTF_OK;
 }
 

@@ -7,9 +7,13 @@ steps (``step_count > max_steps``, utils.py:559).  All envs of a batch share GAM
 all stop at the same step.  Returns what the reference returns per env: the result sign (utils.py:562-569) and the
 counters ``env.metrics`` holds (as tensors; ``VecGridworldCtf.counters``).
 """
+import numpy as np
+
 try:
+    from .harvest import EpisodeHarvest
     from .rollout import BatchedRolloutCollector
 except ImportError:  # pragma: no cover
+    from harvest import EpisodeHarvest
     from rollout import BatchedRolloutCollector
 
 
@@ -29,6 +33,48 @@ def batched_duel(vec, agent, opponent, max_steps=256):
     metrics, caps, _ = vec.counters()
     result = torch.sign(caps[:, 0] - caps[:, 1]).to(torch.int8)
     return dict(result=result, team_flag_captures=caps, metrics=metrics, steps=n_steps)
+
+
+def batched_tournament(vec, agents, opponents, max_steps=256):
+    """Every pairing of ``agents`` (team 0) with ``opponents`` (team 1) in ONE batch: the batched form of the league's pairing
+    loops (reference league_training.py:573-648).  The E envs are cut into ``len(agents) * len(opponents)`` contiguous, equal
+    blocks, agent-major: block (a, b) — group ``a * len(opponents) + b`` — plays ``agents[a]`` against ``opponents[b]``, each env
+    one duel as ``batched_duel`` plays it.  Every policy is called once per step, through ``get_action_and_value(grid, metadata,
+    mask)``, on the rows of the envs it plays in.  One harvest after the last step gives the table.
+    -> dict(episodes int64 [A, B], result_counts int64 [A, B, 3] (team 0 wins, draws, team 1 wins), win_rate float64 [A, B]
+    (team 0's), table int64 [A * B, H] (``harvest.EpisodeHarvest``: ``results(g, table)`` / ``metrics(g, table)``), steps)."""
+    import torch
+
+    A, B, E = len(agents), len(opponents), vec.n_envs
+    if A < 1 or B < 1 or E % (A * B):
+        raise ValueError(f"{E} envs do not divide into {A} x {B} equal blocks")
+    per = E // (A * B)
+    col = BatchedRolloutCollector(vec, 1, 0)  # the policy plumbing of batched_duel
+    dev = vec.device
+    env = torch.arange(E, device=dev)
+    harvest = EpisodeHarvest(vec, A * B, env // per)
+    # rows of opponent b: its block under every agent
+    rows_of = [torch.cat([env[(a * B + b) * per:(a * B + b + 1) * per] for a in range(A)]) for b in range(B)]
+    acts = torch.zeros((E, vec.N_AGENTS), dtype=torch.int8, device=dev)
+    n_steps = min(int(vec.cfg.game_steps), int(max_steps) + 1)
+    vec.reset()
+    with torch.no_grad():
+        for _ in range(n_steps):
+            obs, meta = vec.observe()
+            for a, net in enumerate(agents):
+                sl = slice(a * B * per, (a + 1) * B * per)
+                acts[sl][:, col.trained_idx] = col._policy(net, obs[sl], meta[sl], col.trained_idx)[0].to(torch.int8).transpose(0, 1)
+            for b, net in enumerate(opponents):
+                rows = rows_of[b]
+                act = col._policy(net, obs.index_select(0, rows), meta.index_select(0, rows), col.others_idx)[0]
+                acts[rows[:, None], col.others_idx[None, :]] = act.to(torch.int8).transpose(0, 1)
+            mapped = col.rev_lut[acts.long()]  # team-1 agents act in their flipped view (utils.py:535-551)
+            vec.step(torch.where(col.is_team1[None, :], mapped, acts).contiguous())
+    harvest.update(all_envs=True)
+    table = harvest.table()
+    episodes = table[:, 0].reshape(A, B)
+    counts = table[:, 1:4].reshape(A, B, 3)
+    return dict(episodes=episodes, result_counts=counts, win_rate=counts[:, :, 0] / np.maximum(episodes, 1), table=table, steps=n_steps)
 
 
 def duel_trajectory(vec, agent, opponent, env_index=0, max_steps=256):

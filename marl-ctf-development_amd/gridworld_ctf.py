@@ -479,6 +479,30 @@ class VecGridworldCtf:
         recs = self.save_states(src, out=scratch[:n])
         self.load_states(recs, dst_idx, check=check)
 
+    # -- harvest of finished episodes into per-group results (include/ctf_env.h, ctf_harvest_episodes) ------------------------
+    @property
+    def harvest_words(self):
+        """H = 8 + 13 * N: int64 words of one group's row of a harvest table."""
+        return int(self._lib.ctf_harvest_words(self._h))
+
+    def harvest(self, acc, groups=None, mask=None, all_envs=False):
+        """ADD the results of the envs whose episode ended in the most recent step (``done`` set and ``env_step_count ==
+        GAME_STEPS``; with ``all_envs`` every env as it stands) into ``acc``, int64 [n_groups, harvest_words] on the envs'
+        device: row ``groups[e]`` (int32 [E]; None: row 0) receives env e.  ``mask`` (uint8 [E]): only envs whose byte is
+        non-zero.  One stream-ordered launch; call it once after every step (``harvest.EpisodeHarvest`` owns a table and does).
+        A group id outside [0, n_groups) skips that env and ``status()`` shows ST_BAD_GROUP."""
+        torch = _torch()
+        H = self.harvest_words
+        if not (isinstance(acc, torch.Tensor) and acc.dtype == torch.int64 and acc.is_cuda and acc.device == self.device):
+            raise ValueError(f"harvest: expected an int64 table on {self.device}")
+        if acc.dim() != 2 or acc.shape[0] < 1 or acc.shape[1] != H or not acc.is_contiguous():
+            raise ValueError(f"harvest: expected a contiguous table of shape [n_groups >= 1, {H}], got {list(acc.shape)}")
+        g = None if groups is None else self._check_dev(groups, torch.int32, self.n_envs)
+        m = None if mask is None else self._check_dev(mask, torch.uint8, self.n_envs)
+        _abi.check(self._lib.ctf_harvest_episodes(self._h, g, int(acc.shape[0]), m, _abi.HARVEST_ALL if all_envs else 0,
+                                                  C.c_void_p(acc.data_ptr()), self._stream()), self._lib)
+        return acc
+
     # -- host views ---------------------------------------------------------------------------
     def get_state(self, env_index):
         v = _abi.CtfStateView()
@@ -492,6 +516,27 @@ class VecGridworldCtf:
         bits = C.c_uint32(0)
         _abi.check(self._lib.ctf_status(self._h, C.byref(bits), self._stream()), self._lib)
         return bits.value
+
+
+def metrics_from_counters(counters, team_captures, agent_teams, agent_types, n_agents):
+    """The reference's metrics dict (gridworld_ctf.py:425-470) without the visitation maps, from agent-level counters
+    ``counters[k][i]`` (k in _abi.METRIC_NAMES order) and ``team_captures[t]``: the team_* and agent_type_* entries are sums of
+    the agent-level counters, as in the reference.  One env's counters (``GridworldCtf.metrics``) or sums over many episodes
+    (``harvest.EpisodeHarvest.metrics``)."""
+    out = {"team_wins": {0: 0, 1: 0}}
+    for k, name in enumerate(_abi.METRIC_NAMES):
+        team = {0: 0, 1: 0}
+        by_type = defaultdict(partial(defaultdict, int))
+        agent = defaultdict(int)
+        for i in range(n_agents):
+            val = int(counters[k][i])
+            if val:
+                agent[i] = val
+                team[agent_teams[i]] += val
+                by_type[agent_teams[i]][agent_types[i]] += val
+        out["team_" + name], out["agent_type_" + name], out["agent_" + name] = team, by_type, agent
+    out["team_flag_captures"] = {0: int(team_captures[0]), 1: int(team_captures[1])}
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
@@ -626,19 +671,7 @@ class GridworldCtf:
         """The reference's metrics dict (gridworld_ctf.py:425-470), rebuilt from the device counters:
         team_* and agent_type_* entries are sums of the agent-level counters, as in the reference."""
         v, n, g = self._view, self.N_AGENTS, self.GRID_SIZE
-        out = {"team_wins": {0: 0, 1: 0}}
-        for k, name in enumerate(_abi.METRIC_NAMES):
-            team = {0: 0, 1: 0}
-            by_type = defaultdict(partial(defaultdict, int))
-            agent = defaultdict(int)
-            for i in range(n):
-                val = int(v.metrics[k][i])
-                if val:
-                    agent[i] = val
-                    team[self.AGENT_TEAMS[i]] += val
-                    by_type[self.AGENT_TEAMS[i]][self.AGENT_TYPES[i]] += val
-            out["team_" + name], out["agent_type_" + name], out["agent_" + name] = team, by_type, agent
-        out["team_flag_captures"] = {0: int(v.team_captures[0]), 1: int(v.team_captures[1])}
+        out = metrics_from_counters(v.metrics, v.team_captures, self.AGENT_TEAMS, self.AGENT_TYPES, n)
         vis = defaultdict(partial(np.zeros, (g, g), dtype=np.uint8))
         for i in range(n):
             vis[i] = np.frombuffer(v.visitation[i], dtype=np.uint8, count=g * g).reshape(g, g).copy()

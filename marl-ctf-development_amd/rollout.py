@@ -89,9 +89,9 @@ class BatchedRolloutCollector:
         return bool(self.compact)
 
     def _policy(self, net, obs, meta, idx):
-        """Run one policy over agents `idx` of every env: batch = E * len(idx), agent-major."""
+        """Run one policy over agents `idx` of every env (row) of `obs` / `meta`: batch = E * len(idx), agent-major."""
         torch = self.torch
-        E = self.vec.n_envs
+        E = obs.shape[0]
         grid = obs.index_select(1, idx).transpose(0, 1).reshape((-1,) + tuple(obs.shape[2:])).to(torch.float32)
         md = meta.index_select(1, idx).transpose(0, 1).reshape(-1, meta.shape[2]).to(torch.float32)
         mask = self.mask_flag.index_select(0, idx)[:, None].expand(-1, E).reshape(-1)
