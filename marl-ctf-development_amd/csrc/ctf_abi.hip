@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ctf_device.h"
+#include "ctf_device_scope.h"
 #include "ctf_harvest.h"
 #include "ctf_snapshot.h"
 
@@ -114,20 +115,6 @@ static int store_hint(const ctf_env* h) {
     return all > ((long long)320 << 20);
 }
 
-// remembers and restores the caller's current device
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 #include "ctf_derive.h"
 
 static void free_all(ctf_env* h) {
@@ -151,8 +138,8 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return fail(CTF_E_INVALID, "device %d of %d", device_id, ndev);
-    DeviceGuard guard(device_id);
-    if (!guard.ok) return fail(CTF_E_HIP, "hipSetDevice(%d) failed", device_id);
+    DeviceScope guard(device_id);
+    if (guard.error) return fail(CTF_E_HIP, "hipSetDevice(%d) failed", device_id);
     ctf_env* h = new (std::nothrow) ctf_env();
     if (!h) return fail(CTF_E_NOMEM, "host allocation failed");
     memset(&h->p, 0, sizeof(h->p));
@@ -231,7 +218,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
 extern "C" void ctf_destroy(ctf_env* h) {
     if (!h) return;
     if (h->device >= 0 && h->device < CTF_MAX_DEVICES) g_obs_bytes[h->device].fetch_sub(obs_total(h), std::memory_order_relaxed);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     (void)hipDeviceSynchronize();
     free_all(h);
 }
@@ -246,7 +233,7 @@ extern "C" int32_t ctf_sizeof_state_view(void) { return (int32_t)sizeof(ctf_stat
 
 extern "C" int ctf_seed(ctf_env* h, const uint64_t* py_seeds, const uint64_t* np_seeds, void* stream) {
     if (!h || !py_seeds || !np_seeds) return fail(CTF_E_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     const size_t E = (size_t)h->d.n_envs;
     if (h->d.rng_mode == CTF_RNG_MT19937)
         for (size_t e = 0; e < E; e++)
@@ -270,7 +257,7 @@ extern "C" int ctf_set_rng_state(ctf_env* h, int32_t e, const uint32_t* py, cons
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
     if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_set_rng_state")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(hipDeviceSynchronize());
     const uint32_t* src[2] = {py, np_};
     uint32_t* dev[2] = {nullptr, nullptr};
@@ -296,7 +283,7 @@ extern "C" int ctf_get_rng_state(ctf_env* h, int32_t e, uint32_t* py, uint32_t* 
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
     if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_get_rng_state")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(hipDeviceSynchronize());
     uint32_t* dst[2] = {py, np_};
     for (int k = 0; k < 2; k++) {
@@ -312,7 +299,7 @@ extern "C" int ctf_set_rng_states(ctf_env* h, const uint32_t* py_dev, const uint
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!py_dev && !np_dev) return CTF_OK;
     if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_set_rng_states")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_import_rng(h->d, h->p, py_dev, np_dev, 0, h->d.n_envs, (hipStream_t)stream));
     HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, (hipStream_t)stream));
     return CTF_OK;
@@ -322,7 +309,7 @@ extern "C" int ctf_get_rng_states(ctf_env* h, uint32_t* py_dev, uint32_t* np_dev
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!py_dev && !np_dev) return CTF_OK;
     if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_get_rng_states")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_export_rng(h->d, h->p, py_dev, np_dev, 0, h->d.n_envs, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -330,7 +317,7 @@ extern "C" int ctf_get_rng_states(ctf_env* h, uint32_t* py_dev, uint32_t* np_dev
 extern "C" int ctf_get_rng_counters(ctf_env* h, uint64_t* counters_dev, void* stream) {
     if (!h || !counters_dev) return fail(CTF_E_INVALID, "null argument");
     if (int rc = need_mode(h, CTF_RNG_COUNTER, "ctf_get_rng_counters")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_get_counters(h->d, h->p, (unsigned long long*)counters_dev, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -338,7 +325,7 @@ extern "C" int ctf_get_rng_counters(ctf_env* h, uint64_t* counters_dev, void* st
 extern "C" int ctf_set_rng_counters(ctf_env* h, const uint64_t* counters_dev, void* stream) {
     if (!h || !counters_dev) return fail(CTF_E_INVALID, "null argument");
     if (int rc = need_mode(h, CTF_RNG_COUNTER, "ctf_set_rng_counters")) return rc;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_set_counters(h->d, h->p, (const unsigned long long*)counters_dev, (hipStream_t)stream));
     HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, (hipStream_t)stream));
     return CTF_OK;
@@ -346,14 +333,14 @@ extern "C" int ctf_set_rng_counters(ctf_env* h, const uint64_t* counters_dev, vo
 
 extern "C" int ctf_reset(ctf_env* h, const uint8_t* mask_dev, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_reset(h->d, h->p, mask_dev, 0, (hipStream_t)stream));
     return CTF_OK;
 }
 
 extern "C" int ctf_step(ctf_env* h, const int8_t* actions, float* rw32, double* rw64, uint8_t* done, uint32_t flags, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_step(h->d, h->p, actions, rw32, rw64, done, flags, 1, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -365,7 +352,7 @@ static uint32_t resolve_reverse(const ctf_env* h, uint32_t reverse_mask) {
 extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!obs && !meta) return CTF_OK;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     h->d.obs_store_nt = store_hint(h);
     HIP_TRY(ctf_launch_observe(h->d, h->p, obs, meta, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
     return CTF_OK;
@@ -384,7 +371,7 @@ extern "C" int32_t ctf_observe_stores_hinted(const ctf_env* h, const uint8_t* ob
 extern "C" int ctf_observe_codes(ctf_env* h, uint8_t* codes, uint16_t* meta, uint16_t* selfcells, uint32_t reverse_mask, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!codes && !meta && !selfcells) return CTF_OK;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_observe_codes(h->d, h->p, codes, meta, selfcells, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -392,7 +379,7 @@ extern "C" int ctf_observe_codes(ctf_env* h, uint8_t* codes, uint16_t* meta, uin
 extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, double* rw64, uint8_t* done, uint8_t* obs,
                                 uint16_t* meta, uint32_t reverse_mask, uint32_t flags, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     // (The ring regeneration rides at the tail of the step launch.  Running it as a launch of its own on a second stream, beside
     // the render, was built and measured in round 3: the render lost more than the step kernel gained — 189-191 M against 198 M
     // env-steps/s, profiles/r03_side_stream_ablation.md.)
@@ -467,7 +454,7 @@ static void decode_visitation(const DevCfg& d, const int32_t misc[4], std::vecto
 extern "C" int ctf_get_state(ctf_env* h, int32_t e, ctf_state_view* out) {
     if (!h || !out) return fail(CTF_E_INVALID, "null argument");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     const DevCfg& d = h->d;
     HIP_TRY(hipDeviceSynchronize());
     std::vector<uint8_t> rec((size_t)d.RS), grid((size_t)d.GS);
@@ -548,7 +535,7 @@ extern "C" int ctf_host_step(ctf_env* h, const int8_t* actions, const uint32_t* 
         if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_host_step with generator states")) return rc;
     for (const uint32_t* s : {py_in, np_in})
         if (s && s[CTF_MT_N] > CTF_MT_N) return fail(CTF_E_INVALID, "MT position %u > 624", s[CTF_MT_N]);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     const DevCfg& d = h->d;
     const HostIo L = host_io_layout(d);
     if (!h->hio_host) {
@@ -616,7 +603,7 @@ extern "C" int ctf_host_step(ctf_env* h, const int8_t* actions, const uint32_t* 
 extern "C" int ctf_set_state(ctf_env* h, int32_t e, const ctf_state_view* in) {
     if (!h || !in) return fail(CTF_E_INVALID, "null argument");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     const DevCfg& d = h->d;
     for (int i = 0; i < d.N; i++) {
         if (in->pos[i][0] < 0 || in->pos[i][0] >= d.G || in->pos[i][1] < 0 || in->pos[i][1] >= d.G)
@@ -661,7 +648,7 @@ extern "C" int ctf_set_state(ctf_env* h, int32_t e, const ctf_state_view* in) {
 extern "C" int ctf_export_counters(ctf_env* h, int32_t* metrics_dev, int32_t* captures_dev, int32_t* steps_dev, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!metrics_dev && !captures_dev && !steps_dev) return CTF_OK;
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_export_counters(h->d, h->p, metrics_dev, captures_dev, steps_dev, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -680,7 +667,7 @@ static int snap_args(const ctf_env* h, int32_t n, const void* buf, const char* w
 extern "C" int ctf_save_states(ctf_env* h, const int32_t* src_idx, int32_t n, uint8_t* dst, void* stream) {
     if (int rc = snap_args(h, n, dst, "ctf_save_states")) return rc;
     if (!src_idx && n > h->d.n_envs) return fail(CTF_E_RANGE, "ctf_save_states: n = %d > %d envs", n, h->d.n_envs);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_save_states(snap_layout(h->d, h->p, h->fingerprint), src_idx, n, dst, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -688,7 +675,7 @@ extern "C" int ctf_save_states(ctf_env* h, const int32_t* src_idx, int32_t n, ui
 extern "C" int ctf_load_states(ctf_env* h, const uint8_t* src, const int32_t* dst_idx, int32_t n, void* stream) {
     if (int rc = snap_args(h, n, src, "ctf_load_states")) return rc;
     if (n > h->d.n_envs) return fail(CTF_E_RANGE, "ctf_load_states: n = %d > %d envs", n, h->d.n_envs);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_load_states(snap_layout(h->d, h->p, h->fingerprint), src, dst_idx, n, (hipStream_t)stream));
     return CTF_OK;
 }
@@ -703,14 +690,14 @@ extern "C" int ctf_harvest_episodes(ctf_env* h, const int32_t* group_dev, int32_
     if (!acc_dev) return fail(CTF_E_INVALID, "ctf_harvest_episodes: null table");
     if ((uintptr_t)acc_dev % 8) return fail(CTF_E_INVALID, "ctf_harvest_episodes: the table must be 8-byte aligned");
     if (flags & ~CTF_HARVEST_ALL) return fail(CTF_E_INVALID, "ctf_harvest_episodes: unknown flags 0x%x", flags);
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_harvest(harvest_args(h->d, h->p), group_dev, n_groups, env_mask_dev, flags, acc_dev, (hipStream_t)stream));
     return CTF_OK;
 }
 
 extern "C" int ctf_status(ctf_env* h, uint32_t* out_bits, void* stream) {
     if (!h || !out_bits) return fail(CTF_E_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(out_bits, h->p.status, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemsetAsync(h->p.status, 0, 4, st));
@@ -720,7 +707,7 @@ extern "C" int ctf_status(ctf_env* h, uint32_t* out_bits, void* stream) {
 
 extern "C" int ctf_random_actions(ctf_env* h, int8_t* actions, uint64_t seed, uint32_t step, uint32_t env_offset, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
-    DeviceGuard guard(h->device);
+    DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_random_actions(h->d, actions, seed, step, env_offset, (hipStream_t)stream));
     return CTF_OK;
 }

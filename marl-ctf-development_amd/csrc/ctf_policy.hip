@@ -21,7 +21,7 @@
 // tanh(x) = 1 - 2 / (2^(x * 2 log2 e) + 1): the factor 2 log2 e is folded into the conv weights and biases on the host,
 // so a pair of activations costs 2 v_exp_f32, v_pk_add_f32, 2 v_rcp_f32, v_pk_fma_f32, v_cvt_pk_bf16_f32.
 // fc1 is a plain GEMM and stays with hipBLASLt (through torch).
-#include "ctf_policy_dev.h"
+#include "ctf_policy_host.h"
 
 // One LDS image of this wave ([2 channel halves][rows][8 channels] bf16) -> global memory channels-last ([rows][16 channels]): 16-byte
 // pieces, consecutive lanes write consecutive pieces.
@@ -629,13 +629,12 @@ int ctf_policy_fail(const char* msg) {
     snprintf(g_perr, sizeof(g_perr), "%s", msg);
     return -1;
 }
-static int pfail(const char* msg) { return ctf_policy_fail(msg); }
 
 // ---- deterministic mode: the per-device workspace and the ordered reduction of the blocks' partial sums
 static DetWorkspace g_det[64];
 extern "C" int ctf_policy_set_deterministic(int32_t device_id, float* workspace_dev, int64_t workspace_floats) {
-    if (device_id < 0 || device_id >= 64) return pfail("device_id out of range");
-    if (workspace_dev && (workspace_floats < 1 || ((uintptr_t)workspace_dev & 15))) return pfail("workspace: 16-byte aligned, at least one float");
+    if (device_id < 0 || device_id >= 64) return ctf_policy_fail("device_id out of range");
+    if (workspace_dev && (workspace_floats < 1 || ((uintptr_t)workspace_dev & 15))) return ctf_policy_fail("workspace: 16-byte aligned, at least one float");
     g_det[device_id].ptr = workspace_dev;
     g_det[device_id].floats = workspace_dev ? workspace_floats : 0;
     return 0;
@@ -668,9 +667,7 @@ hipError_t ctf_policy_det_reduce(const float* part, int n_blocks, int64_t stride
 }
 
 // compute units of a device, looked up once per device and thread (hipGetDeviceProperties is not free)
-static int policy_n_cus(int device_id);
-int ctf_policy_cus(int device_id) { return policy_n_cus(device_id); }
-static int policy_n_cus(int device_id) {
+int ctf_policy_cus(int device_id) {
     static thread_local int cus_of[64];
     if (device_id >= 0 && device_id < 64 && cus_of[device_id]) return cus_of[device_id];
     hipDeviceProp_t prop;
@@ -690,57 +687,39 @@ extern "C" int ctf_policy_features(const uint8_t* codes_dev, const uint16_t* met
                                    const float* conv2_bias_dev, uint16_t* act_dev, const uint16_t* shared_view_selfcell_dev,
                                    int32_t device_id, void* stream) {
     if (!codes_dev || !meta_dev || !agent_sel || !conv1_frag_dev || !conv1_bias_dev || !conv2_frag_dev || !conv2_bias_dev || !act_dev)
-        return pfail("null argument");
-    if (grid_size < 5 || grid_size > 32) return pfail("grid_size outside 5..32");
-    if (n_envs < 1 || n_agents < 1 || n_agents > 16 || n_sel < 1 || n_sel > 16) return pfail("n_envs / n_agents / n_sel out of range");
-    if (meta_len < 2 || (meta_len & 1)) return pfail("meta_len must be even (2N + 6)");
-    if (((uintptr_t)act_dev & 15) || ((uintptr_t)meta_dev & 3)) return pfail("act_dev must be 16-byte, meta_dev 4-byte aligned");
-    if ((int64_t)n_envs * n_sel > 0x7FFFFFFF) return pfail("too many samples for one launch");
+        return ctf_policy_fail("null argument");
+    if (grid_size < 5 || grid_size > 32) return ctf_policy_fail("grid_size outside 5..32");
+    if (n_envs < 1 || n_agents < 1 || n_agents > 16 || n_sel < 1 || n_sel > 16) return ctf_policy_fail("n_envs / n_agents / n_sel out of range");
+    if (meta_len < 2 || (meta_len & 1)) return ctf_policy_fail("meta_len must be even (2N + 6)");
+    if (((uintptr_t)act_dev & 15) || ((uintptr_t)meta_dev & 3)) return ctf_policy_fail("act_dev must be 16-byte, meta_dev 4-byte aligned");
+    if ((int64_t)n_envs * n_sel > 0x7FFFFFFF) return ctf_policy_fail("too many samples for one launch");
     PolicyArgs a;
     a.codes = codes_dev; a.meta = meta_dev; a.act = act_dev;
     a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
     a.w2frag = (const u32x4_t*)conv2_frag_dev; a.b2 = conv2_bias_dev;
     a.n_envs = n_envs; a.N = n_agents; a.G = grid_size; a.M = meta_len; a.n_sel = n_sel;
     a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    a.sel_pack = 0;
     a.h0_out = nullptr; a.h1_out = nullptr;
-    for (int k = 0; k < n_sel; k++) {
-        if (agent_sel[k] < 0 || agent_sel[k] >= n_agents) return pfail("agent_sel entry out of range");
-        a.sel_pack |= (uint64_t)agent_sel[k] << (4 * k);
-    }
-    const int G1 = grid_size - 2, G2 = grid_size - 4;
-    a.inv_g1 = (65536 + G1 - 1) / G1;
-    a.inv_g2 = (65536 + G2 - 1) / G2;
-    for (int p = 0; p < G1 * G1; p++)
-        if ((int)(((uint32_t)p * a.inv_g1) >> 16) != p / G1) return pfail("internal: reciprocal of G-2 not exact");
-    for (int p = 0; p < G2 * G2; p++)
-        if ((int)(((uint32_t)p * a.inv_g2) >> 16) != p / G2) return pfail("internal: reciprocal of G-4 not exact");
+    if (pol_pack_sel(agent_sel, n_sel, n_agents, 16, &a.sel_pack)) return -1;
+    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
 
-    const int n_cus = policy_n_cus(device_id);
-    if (!n_cus) return pfail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     const int per_wave = pol_h0_bytes(grid_size) + pol_h1_bytes(grid_size);
     int wpb = 4;
     while (wpb > 1 && wpb * per_wave > 64 * 1024) wpb >>= 1;
-    if (const char* ov = getenv("CTF_POLICY_WPB")) {  // profiling only
-        const int v = atoi(ov);
-        if (v >= 1 && v <= wpb) wpb = v;
-    }
+    wpb = pol_env_int("CTF_POLICY_WPB", 1, wpb, wpb);  // profiling only
     const size_t sh = (size_t)wpb * per_wave;
     int per_cu = (int)((160 * 1024) / sh);
     if (per_cu < 1) per_cu = 1;
     if (per_cu * wpb > 12) per_cu = 12 / wpb;  // 3 waves per SIMD: what the register budget allows
-    if (const char* ov = getenv("CTF_POLICY_BLOCKS_PER_CU")) {  // profiling only: occupancy scaling
-        const int v = atoi(ov);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
+    per_cu = pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, per_cu, per_cu);  // profiling only: occupancy scaling
     const int S = n_envs * n_sel;
     int blocks = (S + wpb - 1) / wpb;
     if (blocks > n_cus * per_cu) blocks = n_cus * per_cu;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
     if (shared_view_selfcell_dev && n_sel <= 4 && (grid_size == 15 || grid_size == 11)) {
         // agents sharing a view: one wave per env does the shared work once and a small patch per agent
         TeamArgs ta;
@@ -750,32 +729,15 @@ extern "C" int ctf_policy_features(const uint8_t* codes_dev, const uint16_t* met
         // ONE block per CU, one wave per SIMD: measured 1.12 ms for the two teams of an arena step against 1.32 / 1.36 with two /
         // three blocks — every wave of this kernel keeps A activation rows open at once, and the more such streams a CU runs
         // the worse its store path does (the per-agent kernel, one row per wave, is the other way round: 1.80 / 1.57 / 1.51)
-        int team_per_cu = 1;
-        if (const char* ov = getenv("CTF_POLICY_BLOCKS_PER_CU")) team_per_cu = atoi(ov) >= 1 ? atoi(ov) : 1;  // profiling only
+        int team_per_cu = pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, 0x7FFFFFFF, 1);  // profiling only
         if (team_per_cu > per_cu) team_per_cu = per_cu;
         int tblocks = (n_envs + wpb - 1) / wpb;
         if (tblocks > n_cus * team_per_cu) tblocks = n_cus * team_per_cu;
-        if (grid_size == 15) {
-            if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features_team<15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features_team<15>, dim3(tblocks), dim3(wpb * WAVE), sh, st, ta);
-        } else {
-            if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features_team<11>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features_team<11>, dim3(tblocks), dim3(wpb * WAVE), sh, st, ta);
-        }
-    } else if (grid_size == 15) {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features<15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features<15>, dim3(blocks), dim3(wpb * WAVE), sh, st, a);
-    } else if (grid_size == 11) {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features<11>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features<11>, dim3(blocks), dim3(wpb * WAVE), sh, st, a);
-    } else {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features<0>, dim3(blocks), dim3(wpb * WAVE), sh, st, a);
+        return pol_finish(pol_launch(grid_size == 15 ? k_policy_features_team<15> : k_policy_features_team<11>, tblocks, wpb * WAVE, sh, st, ta));
     }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    void (*kernel)(PolicyArgs) = k_policy_features<15>;
+    if (grid_size != 15) kernel = grid_size == 11 ? k_policy_features<11> : k_policy_features<0>;
+    return pol_finish(pol_launch(kernel, blocks, wpb * WAVE, sh, st, a));
 }
 
 typedef short i16x4_t __attribute__((ext_vector_type(4)));
@@ -837,7 +799,8 @@ __global__ void __launch_bounds__(256) k_policy_front_dgrad(DgradArgs a) {
     static_assert(!W2 || (RA + 1 < G && H1R > G1), "the zero rows the position contraction reads exist");
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), wpb = blockDim.x / WAVE;
-    uint8_t* zp = (uint8_t*)lds + wave * (ZB + 2 * H1A);
+    static_assert(ZB + 2 * H1A == pol_dgrad_wave_bytes(TG, W2), "the layout constants and the launch's LDS size agree");
+    uint8_t* zp = (uint8_t*)lds + wave * pol_dgrad_wave_bytes(TG, W2);
     uint8_t* h1 = zp + ZB;
     u32x4_t w2t[9];
 #pragma unroll
@@ -1044,58 +1007,47 @@ __global__ void __launch_bounds__(256) k_policy_front_dgrad(DgradArgs a) {
     }
 }
 
+// deterministic mode: the blocks' slices of a.part -> the gradients k_policy_front_dgrad was asked for, in block order
+static hipError_t dgrad_reduce_parts(const DgradArgs& a, int blocks, hipStream_t st) {
+    hipError_t err = hipSuccess;
+    if (!a.part) return err;
+    if (a.dw2) err = ctf_policy_det_reduce(a.part, blocks, DGRAD_PART, 32 * 16 * 9, a.dw2, st);
+    if (err == hipSuccess && a.db2) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9, blocks, DGRAD_PART, 32, a.db2, st);
+    if (err == hipSuccess && a.db1) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9 + 32, blocks, DGRAD_PART, 16, a.db1, st);
+    return err;
+}
+
 extern "C" int ctf_policy_front_dgrad(const uint16_t* d_act_dev, const uint16_t* act_dev, const uint16_t* h1_dev, const void* conv2_t_frag_dev,
                                       int64_t n_samples, int32_t grid_size, int32_t meta_len, uint16_t* dz2_dev, uint16_t* dz1_dev,
                                       float* bias2_grad_dev, float* bias1_grad_dev, int32_t device_id, void* stream) {
-    if (!d_act_dev || !act_dev || !h1_dev || !conv2_t_frag_dev || !dz2_dev || !dz1_dev) return pfail("null argument");
-    if (grid_size != 15 && grid_size != 11) return pfail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return pfail("n_samples out of range");
-    if (((uintptr_t)d_act_dev | (uintptr_t)act_dev | (uintptr_t)dz2_dev | (uintptr_t)dz1_dev) & 7) return pfail("8-byte alignment");
-    if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev) & 15) return pfail("h1_dev / conv2_t_frag_dev must be 16-byte aligned");
+    if (!d_act_dev || !act_dev || !h1_dev || !conv2_t_frag_dev || !dz2_dev || !dz1_dev) return ctf_policy_fail("null argument");
+    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
+    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (((uintptr_t)d_act_dev | (uintptr_t)act_dev | (uintptr_t)dz2_dev | (uintptr_t)dz1_dev) & 7) return ctf_policy_fail("8-byte alignment");
+    if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev) & 15) return ctf_policy_fail("h1_dev / conv2_t_frag_dev must be 16-byte aligned");
     if (!n_samples) return 0;
     DgradArgs a;
     a.d_act = d_act_dev; a.act = act_dev; a.h1 = h1_dev; a.w2t = (const u32x4_t*)conv2_t_frag_dev; a.dz2 = dz2_dev; a.dz1 = dz1_dev;
     a.db2 = bias2_grad_dev; a.db1 = bias1_grad_dev; a.dw2 = nullptr; a.S = n_samples; a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    const int G1 = grid_size - 2, G2 = grid_size - 4;
-    a.inv_g1 = (65536 + G1 - 1) / G1;
-    a.inv_g2 = (65536 + G2 - 1) / G2;
-    for (int p = 0; p < G1 * G1; p++)
-        if ((int)(((uint32_t)p * a.inv_g1) >> 16) != p / G1) return pfail("internal: reciprocal of G-2 not exact");
-    for (int p = 0; p < G2 * G2; p++)
-        if ((int)(((uint32_t)p * a.inv_g2) >> 16) != p / G2) return pfail("internal: reciprocal of G-4 not exact");
-    const int n_cus = policy_n_cus(device_id);
-    if (!n_cus) return pfail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
+    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     const int wpb = 4;
-    const int per_wave = 4 * grid_size * grid_size * 16 + 2 * ((((G1 * G1) + 15) >> 4) << 4) * 16;
-    const size_t sh = (size_t)wpb * per_wave;
+    const size_t sh = pol_dgrad_block_bytes(grid_size, false, wpb);
     int per_cu = (int)((160 * 1024) / sh);
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 2) per_cu = 2;
     int64_t blocks = (n_samples + wpb - 1) / wpb;
     if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
     const DetWorkspace det = ctf_policy_det(device_id);
     a.part = (det.ptr && (a.db2 || a.db1)) ? det.ptr : nullptr;
-    if (a.part && blocks * DGRAD_PART > det.floats) err = hipErrorOutOfMemory;
-    if (err != hipSuccess) {
-    } else if (grid_size == 15) {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_front_dgrad<15, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_dgrad<15, false>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-    } else {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_front_dgrad<11, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_dgrad<11, false>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-    }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess && a.part && a.db2) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9, (int)blocks, DGRAD_PART, 32, a.db2, st);
-    if (err == hipSuccess && a.part && a.db1) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9 + 32, (int)blocks, DGRAD_PART, 16, a.db1, st);
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err == hipErrorOutOfMemory) return pfail("deterministic mode: the registered workspace is too small for this launch (ctf_policy_set_deterministic)");
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    if (a.part && blocks * DGRAD_PART > det.floats) return pol_finish(POL_WORKSPACE_TOO_SMALL);
+    hipError_t err = pol_launch(grid_size == 15 ? k_policy_front_dgrad<15, false> : k_policy_front_dgrad<11, false>, blocks, wpb * WAVE, sh, st, a);
+    if (err == hipSuccess) err = dgrad_reduce_parts(a, (int)blocks, st);
+    return pol_finish(err);
 }
 
 // ---- the two WEIGHT gradients of the training front, contraction over positions on the matrix cores (grid_size 11 / 15)
@@ -1136,7 +1088,8 @@ __global__ void __launch_bounds__(128) k_policy_front_wgrad(WgradArgs a) {
     constexpr int NPB = FROM_CODES ? PI : PI * 2, NB = (NPB + WAVE - 1) / WAVE;  // code bytes / 16-byte pieces of the activation image
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), wpb = blockDim.x / WAVE;
-    uint8_t* A = (uint8_t*)lds + wave * (A_BYTES + B_BYTES);
+    static_assert(RA == pol_wgrad_rows(GO) && A_BYTES + B_BYTES == pol_wgrad_wave_bytes(GO, CO), "the layout constants and the launch's LDS size agree");
+    uint8_t* A = (uint8_t*)lds + wave * pol_wgrad_wave_bytes(GO, CO);
     uint8_t* B = A + A_BYTES;
     {   // zeros everywhere once: the A rows / columns past the image and the B rows / columns past the image stay zero
         const u32x4_t z = {0u, 0u, 0u, 0u};
@@ -1252,54 +1205,49 @@ __global__ void __launch_bounds__(128) k_policy_front_wgrad(WgradArgs a) {
     }
 }
 
+// One weight gradient: the launch (two waves per block, at most four blocks = two waves per SIMD on a CU) and, in deterministic mode,
+// the ordered sum of the blocks' slices into a.dw.
+template <int GO, int CO, bool FROM_CODES>
+static hipError_t launch_front_wgrad(WgradArgs a, int n_cus, int device_id, hipStream_t st) {
+    const int wpb = 2;
+    const size_t sh = pol_wgrad_block_bytes(GO, CO, wpb);
+    int per_cu = (int)((160 * 1024) / sh);
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 4) per_cu = 4;
+    int64_t blocks = (a.S + wpb - 1) / wpb;
+    if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
+    const DetWorkspace det = ctf_policy_det(device_id);
+    a.part = det.ptr;
+    if (a.part && blocks * 9 * CO * 16 > det.floats) return POL_WORKSPACE_TOO_SMALL;
+    hipError_t err = pol_launch(k_policy_front_wgrad<GO, CO, FROM_CODES>, blocks, wpb * WAVE, sh, st, a);
+    if (err == hipSuccess && a.part) err = ctf_policy_det_reduce(a.part, (int)blocks, 9 * CO * 16, 9 * CO * 16, a.dw, st);
+    return err;
+}
+
 extern "C" int ctf_policy_front_wgrad(const uint16_t* dz2_dev, const uint16_t* h1_dev, const uint16_t* dz1_dev, const uint8_t* codes_dev,
                                       int64_t n_samples, int32_t grid_size, float* dw2_dev, float* dw1_dev, int32_t device_id, void* stream) {
-    if (!dz2_dev || !h1_dev || !dz1_dev || !codes_dev || !dw2_dev || !dw1_dev) return pfail("null argument");
-    if (grid_size != 15 && grid_size != 11) return pfail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return pfail("n_samples out of range");
-    if (((uintptr_t)dz2_dev | (uintptr_t)h1_dev | (uintptr_t)dz1_dev) & 15) return pfail("16-byte alignment");
+    if (!dz2_dev || !h1_dev || !dz1_dev || !codes_dev || !dw2_dev || !dw1_dev) return ctf_policy_fail("null argument");
+    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
+    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (((uintptr_t)dz2_dev | (uintptr_t)h1_dev | (uintptr_t)dz1_dev) & 15) return ctf_policy_fail("16-byte alignment");
     if (!n_samples) return 0;
-    const int n_cus = policy_n_cus(device_id);
-    if (!n_cus) return pfail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
-    const int wpb = 2;
-    auto launch = [&](auto kernel, int go, int co, const WgradArgs& a) {
-        const int ra = go + 1 + ((go & 1) ? 0 : 1), rb = ra + 2;
-        size_t sh = (size_t)wpb * ((size_t)ra * 16 * co * 2 + (size_t)rb * 18 * 32);  // k_policy_front_wgrad's A_BYTES + B_BYTES per wave
-        const size_t red = (size_t)wpb * 9 * co * 16 * 4;
-        if (sh < red) sh = red;
-        int per_cu = (int)((160 * 1024) / sh);
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 4) per_cu = 4;  // 8 waves per CU = 2 per SIMD
-        int64_t blocks = (a.S + wpb - 1) / wpb;
-        if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
-        WgradArgs b = a;
-        const DetWorkspace det = ctf_policy_det(device_id);
-        b.part = det.ptr;
-        if (err == hipSuccess && b.part && blocks * 9 * co * 16 > det.floats) err = hipErrorOutOfMemory;
-        if (err == hipSuccess && sh > 48 * 1024) err = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, b);
-        if (err == hipSuccess && b.part) err = ctf_policy_det_reduce(b.part, (int)blocks, 9 * co * 16, 9 * co * 16, b.dw, st);
-    };
     WgradArgs a2, a1;
     a2.grad = dz2_dev; a2.img = h1_dev; a2.codes = nullptr; a2.dw = dw2_dev; a2.S = n_samples;
     a1.grad = dz1_dev; a1.img = nullptr; a1.codes = codes_dev; a1.dw = dw1_dev; a1.S = n_samples;
+    hipError_t err;
     if (grid_size == 15) {
-        launch(k_policy_front_wgrad<11, 32, false>, 11, 32, a2);
-        launch(k_policy_front_wgrad<13, 16, true>, 13, 16, a1);
+        err = launch_front_wgrad<11, 32, false>(a2, n_cus, device_id, st);
+        if (err == hipSuccess) err = launch_front_wgrad<13, 16, true>(a1, n_cus, device_id, st);
     } else {
-        launch(k_policy_front_wgrad<7, 32, false>, 7, 32, a2);
-        launch(k_policy_front_wgrad<9, 16, true>, 9, 16, a1);
+        err = launch_front_wgrad<7, 32, false>(a2, n_cus, device_id, st);
+        if (err == hipSuccess) err = launch_front_wgrad<9, 16, true>(a1, n_cus, device_id, st);
     }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err == hipErrorOutOfMemory) return pfail("deterministic mode: the registered workspace is too small for this launch (ctf_policy_set_deterministic)");
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(err);
 }
 
 // The whole backward of the training front: conv2's data AND weight gradient in one pass (k_policy_front_dgrad<.., true>: dz2 never
@@ -1308,82 +1256,35 @@ extern "C" int ctf_policy_front_backward(const uint16_t* d_act_dev, const uint16
                                          const void* conv2_t_frag_dev, int64_t n_samples, int32_t grid_size, int32_t meta_len,
                                          uint16_t* dz1_dev, float* dw2_dev, float* dw1_dev, float* bias2_grad_dev, float* bias1_grad_dev,
                                          int32_t device_id, void* stream) {
-    if (!d_act_dev || !act_dev || !h1_dev || !codes_dev || !conv2_t_frag_dev || !dz1_dev || !dw2_dev || !dw1_dev) return pfail("null argument");
-    if (grid_size != 15 && grid_size != 11) return pfail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return pfail("n_samples out of range");
-    if (((uintptr_t)d_act_dev | (uintptr_t)act_dev) & 7) return pfail("8-byte alignment");
-    if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev | (uintptr_t)dz1_dev) & 15) return pfail("h1_dev / conv2_t_frag_dev / dz1_dev must be 16-byte aligned");
+    if (!d_act_dev || !act_dev || !h1_dev || !codes_dev || !conv2_t_frag_dev || !dz1_dev || !dw2_dev || !dw1_dev) return ctf_policy_fail("null argument");
+    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
+    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (((uintptr_t)d_act_dev | (uintptr_t)act_dev) & 7) return ctf_policy_fail("8-byte alignment");
+    if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev | (uintptr_t)dz1_dev) & 15) return ctf_policy_fail("h1_dev / conv2_t_frag_dev / dz1_dev must be 16-byte aligned");
     if (!n_samples) return 0;
     DgradArgs a;
     a.d_act = d_act_dev; a.act = act_dev; a.h1 = h1_dev; a.w2t = (const u32x4_t*)conv2_t_frag_dev; a.dz2 = nullptr; a.dz1 = dz1_dev;
     a.db2 = bias2_grad_dev; a.db1 = bias1_grad_dev; a.dw2 = dw2_dev; a.S = n_samples; a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    const int G1 = grid_size - 2, G2 = grid_size - 4;
-    a.inv_g1 = (65536 + G1 - 1) / G1;
-    a.inv_g2 = (65536 + G2 - 1) / G2;
-    for (int p = 0; p < G1 * G1; p++)
-        if ((int)(((uint32_t)p * a.inv_g1) >> 16) != p / G1) return pfail("internal: reciprocal of G-2 not exact");
-    for (int p = 0; p < G2 * G2; p++)
-        if ((int)(((uint32_t)p * a.inv_g2) >> 16) != p / G2) return pfail("internal: reciprocal of G-4 not exact");
-    const int n_cus = policy_n_cus(device_id);
-    if (!n_cus) return pfail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
+    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
+    // the fused pass: four waves per block, one block per CU (the padded images are 25 KB per wave, the registers one wave per SIMD)
+    const int wpb = 4;
+    const size_t sh = pol_dgrad_block_bytes(grid_size, true, wpb);
+    int64_t blocks = (n_samples + wpb - 1) / wpb;
+    if (blocks > (int64_t)n_cus) blocks = n_cus;
     const DetWorkspace det = ctf_policy_det(device_id);
-    {   // the fused pass: four waves per block, one block per CU (the padded images are 25 KB per wave, the registers one wave per SIMD)
-        const int wpb = 4;
-        const int ra = G2 + 1 + ((G2 & 1) ? 0 : 1);
-        const size_t per_wave = (size_t)4 * grid_size * 18 * 16 + (size_t)2 * (ra + 2) * 18 * 16;  // k_policy_front_dgrad<.., true>: ZB + 2 H1A
-        size_t sh = (size_t)wpb * per_wave;
-        const size_t red = (size_t)wpb * 9 * 32 * 16 * 4;
-        if (sh < red) sh = red;
-        int64_t blocks = (n_samples + wpb - 1) / wpb;
-        if (blocks > (int64_t)n_cus) blocks = n_cus;
-        a.part = det.ptr;
-        if (a.part && blocks * DGRAD_PART > det.floats) err = hipErrorOutOfMemory;
-        if (err != hipSuccess) {
-        } else if (grid_size == 15) {
-            err = hipFuncSetAttribute((const void*)k_policy_front_dgrad<15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_dgrad<15, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-        } else {
-            err = hipFuncSetAttribute((const void*)k_policy_front_dgrad<11, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_dgrad<11, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-        }
-        if (err == hipSuccess && a.part) err = ctf_policy_det_reduce(a.part, (int)blocks, DGRAD_PART, 32 * 16 * 9, a.dw2, st);
-        if (err == hipSuccess && a.part && a.db2) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9, (int)blocks, DGRAD_PART, 32, a.db2, st);
-        if (err == hipSuccess && a.part && a.db1) err = ctf_policy_det_reduce(a.part + 32 * 16 * 9 + 32, (int)blocks, DGRAD_PART, 16, a.db1, st);
-    }
-    {   // conv1's weight gradient (as in ctf_policy_front_wgrad)
-        const int wpb = 2, go = G1, co = 16;
-        const int ra = go + 1 + ((go & 1) ? 0 : 1), rb = ra + 2;
-        size_t sh = (size_t)wpb * ((size_t)ra * 16 * co * 2 + (size_t)rb * 18 * 32);
-        const size_t red = (size_t)wpb * 9 * co * 16 * 4;
-        if (sh < red) sh = red;
-        int per_cu = (int)((160 * 1024) / sh);
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 4) per_cu = 4;
-        int64_t blocks = (n_samples + wpb - 1) / wpb;
-        if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
-        WgradArgs a1;
-        a1.grad = dz1_dev; a1.img = nullptr; a1.codes = codes_dev; a1.dw = dw1_dev; a1.S = n_samples;
-        a1.part = det.ptr;
-        if (err == hipSuccess && a1.part && blocks * 9 * co * 16 > det.floats) err = hipErrorOutOfMemory;
-        if (grid_size == 15) {
-            if (err == hipSuccess && sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_front_wgrad<13, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_wgrad<13, 16, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a1);
-        } else {
-            if (err == hipSuccess && sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_front_wgrad<9, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-            if (err == hipSuccess) hipLaunchKernelGGL((k_policy_front_wgrad<9, 16, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a1);
-        }
-        if (err == hipSuccess && a1.part) err = ctf_policy_det_reduce(a1.part, (int)blocks, 9 * co * 16, 9 * co * 16, a1.dw, st);
-    }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err == hipErrorOutOfMemory) return pfail("deterministic mode: the registered workspace is too small for this launch (ctf_policy_set_deterministic)");
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    a.part = det.ptr;
+    if (a.part && blocks * DGRAD_PART > det.floats) return pol_finish(POL_WORKSPACE_TOO_SMALL);
+    hipError_t err = pol_launch(grid_size == 15 ? k_policy_front_dgrad<15, true> : k_policy_front_dgrad<11, true>, blocks, wpb * WAVE, sh, st, a);
+    if (err == hipSuccess) err = dgrad_reduce_parts(a, (int)blocks, st);
+    WgradArgs a1;  // conv1's weight gradient
+    a1.grad = dz1_dev; a1.img = nullptr; a1.codes = codes_dev; a1.dw = dw1_dev; a1.S = n_samples;
+    if (err == hipSuccess) err = grid_size == 15 ? launch_front_wgrad<13, 16, true>(a1, n_cus, device_id, st) : launch_front_wgrad<9, 16, true>(a1, n_cus, device_id, st);
+    return pol_finish(err);
 }
 
 extern "C" int ctf_policy_features_train(const uint8_t* codes_dev, const uint16_t* meta_dev, int64_t n_samples, int32_t grid_size,
@@ -1391,12 +1292,12 @@ extern "C" int ctf_policy_features_train(const uint8_t* codes_dev, const uint16_
                                          const void* conv2_frag_dev, const float* conv2_bias_dev, uint16_t* act_dev, uint16_t* h0_dev,
                                          uint16_t* h1_dev, int32_t device_id, void* stream) {
     if (!codes_dev || !meta_dev || !conv1_frag_dev || !conv1_bias_dev || !conv2_frag_dev || !conv2_bias_dev || !act_dev || !h1_dev)
-        return pfail("null argument");
-    if (grid_size != 15 && grid_size != 11) return pfail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 1 || n_samples > 0x7FFFFFFF) return pfail("n_samples out of range");
-    if (meta_len < 2 || (meta_len & 1)) return pfail("meta_len must be even (2N + 6)");
+        return ctf_policy_fail("null argument");
+    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
+    if (n_samples < 1 || n_samples > 0x7FFFFFFF) return ctf_policy_fail("n_samples out of range");
+    if (meta_len < 2 || (meta_len & 1)) return ctf_policy_fail("meta_len must be even (2N + 6)");
     if (((uintptr_t)act_dev & 15) || ((uintptr_t)h0_dev & 15) || ((uintptr_t)h1_dev & 15) || ((uintptr_t)meta_dev & 3))
-        return pfail("act_dev / h0_dev / h1_dev must be 16-byte, meta_dev 4-byte aligned");
+        return ctf_policy_fail("act_dev / h0_dev / h1_dev must be 16-byte, meta_dev 4-byte aligned");
     PolicyArgs a;
     a.codes = codes_dev; a.meta = meta_dev; a.act = act_dev;
     a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
@@ -1405,18 +1306,11 @@ extern "C" int ctf_policy_features_train(const uint8_t* codes_dev, const uint16_
     a.Kp = ctf_policy_act_stride(grid_size, meta_len);
     a.sel_pack = 0;
     a.h0_out = h0_dev; a.h1_out = h1_dev;
-    const int G1 = grid_size - 2, G2 = grid_size - 4;
-    a.inv_g1 = (65536 + G1 - 1) / G1;
-    a.inv_g2 = (65536 + G2 - 1) / G2;
-    for (int p = 0; p < G1 * G1; p++)
-        if ((int)(((uint32_t)p * a.inv_g1) >> 16) != p / G1) return pfail("internal: reciprocal of G-2 not exact");
-    for (int p = 0; p < G2 * G2; p++)
-        if ((int)(((uint32_t)p * a.inv_g2) >> 16) != p / G2) return pfail("internal: reciprocal of G-4 not exact");
-    const int n_cus = policy_n_cus(device_id);
-    if (!n_cus) return pfail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
+    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     const int per_wave = pol_h0_bytes(grid_size) + pol_h1_bytes(grid_size);
     const int wpb = 4;
     const size_t sh = (size_t)wpb * per_wave;
@@ -1424,19 +1318,7 @@ extern "C" int ctf_policy_features_train(const uint8_t* codes_dev, const uint16_
     if (per_cu * wpb > 12) per_cu = 12 / wpb;  // 3 waves per SIMD, as in ctf_policy_features
     int64_t blocks = (n_samples + wpb - 1) / wpb;
     if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
-    if (grid_size == 15) {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features<15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_features<15, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-    } else {
-        if (sh > 48 * 1024) err = hipFuncSetAttribute((const void*)k_policy_features<11, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_features<11, true>), dim3((unsigned)blocks), dim3(wpb * WAVE), sh, st, a);
-    }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(pol_launch(grid_size == 15 ? k_policy_features<15, true> : k_policy_features<11, true>, blocks, wpb * WAVE, sh, (hipStream_t)stream, a));
 }
 
 extern "C" int ctf_policy_head(const uint16_t* fc1_out_dev, int64_t n_samples, const void* fc2_frag_dev, const float* fc2_bias_dev,
@@ -1446,33 +1328,23 @@ extern "C" int ctf_policy_head(const uint16_t* fc1_out_dev, int64_t n_samples, c
                                int32_t device_id, void* stream) {
     if (!fc1_out_dev || !fc2_frag_dev || !fc2_bias_dev || !head_frag_dev || !head_bias_dev || !action_dev || !logprob_dev ||
         !entropy_dev || !value_dev)
-        return pfail("null argument");
-    if (n_samples < 1) return pfail("n_samples must be >= 1");
-    if (n_actions < 1 || n_actions > 15) return pfail("n_actions outside 1..15");
-    if ((uintptr_t)fc1_out_dev & 15) return pfail("fc1_out_dev must be 16-byte aligned");
+        return ctf_policy_fail("null argument");
+    if (n_samples < 1) return ctf_policy_fail("n_samples must be >= 1");
+    if (n_actions < 1 || n_actions > 15) return ctf_policy_fail("n_actions outside 1..15");
+    if ((uintptr_t)fc1_out_dev & 15) return ctf_policy_fail("fc1_out_dev must be 16-byte aligned");
     HeadArgs a;
     a.y1 = fc1_out_dev; a.fc2_frag = (const u32x4_t*)fc2_frag_dev; a.fc2_bias = fc2_bias_dev;
     a.head_frag = (const u32x4_t*)head_frag_dev; a.head_bias = head_bias_dev;
     a.mask = mask_decision_dev; a.given = given_action_dev;
     a.action = action_dev; a.logprob = logprob_dev; a.entropy = entropy_dev; a.value = value_dev; a.logits = logits_dev;
     a.B = n_samples; a.A = n_actions; a.seed = seed; a.offset = offset;
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return pfail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return pfail("hipSetDevice failed");
-    const int n_cus = policy_n_cus(device_id);
-    hipError_t err = n_cus ? hipSuccess : hipErrorInvalidDevice;
-    if (err == hipSuccess) {
-        const size_t sh = (size_t)HEAD_TILE * HEAD_XS_ROW;  // 66 KB: the stage a/b image; the stage c/d image is smaller
-        static_assert(HEAD_TILE * HEAD_XS_ROW >= HEAD_TILE * HEAD_HS_ROW, "hs aliases xs");
-        err = hipFuncSetAttribute((const void*)k_policy_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) {
-            const int64_t tiles = (n_samples + HEAD_TILE - 1) / HEAD_TILE;
-            const int64_t cap = (int64_t)n_cus * 2;
-            hipLaunchKernelGGL(k_policy_head, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(256), sh, (hipStream_t)stream, a);
-            err = hipGetLastError();
-        }
-    }
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err != hipSuccess) return pfail(hipGetErrorString(err));
-    return 0;
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
+    const int n_cus = ctf_policy_cus(device_id);
+    if (!n_cus) return pol_finish(hipErrorInvalidDevice);
+    const size_t sh = (size_t)HEAD_TILE * HEAD_XS_ROW;  // 66 KB: the stage a/b image; the stage c/d image is smaller
+    static_assert(HEAD_TILE * HEAD_XS_ROW >= HEAD_TILE * HEAD_HS_ROW, "hs aliases xs");
+    const int64_t tiles = (n_samples + HEAD_TILE - 1) / HEAD_TILE;
+    const int64_t cap = (int64_t)n_cus * 2;
+    return pol_finish(pol_launch(k_policy_head, tiles < cap ? tiles : cap, 256, sh, (hipStream_t)stream, a));
 }

@@ -1,5 +1,6 @@
 // ctf_policy_dev.h — device-side helpers shared by the policy kernels (ctf_policy.hip, ctf_policy_fact.hip): vector types, the
-// packed tanh, the hand-placed (compiler-untracked) prefetch loads and their counted waits.
+// packed tanh, the hand-placed (compiler-untracked) prefetch loads and their counted waits, and the LDS sizes kernel and host share.
+// (The host side of the entry points is ctf_policy_host.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,19 +16,6 @@
 //   bit5 team kernel: half of the shared activation stores skipped, bit6 team kernel: rows env-major
 #ifndef POL_ABLATE
 #define POL_ABLATE 0
-// host side: make device_id current for the duration of an entry point, then put the caller's device back
-struct DeviceScope {
-    int prev = -1, want;
-    bool ok = true;
-    explicit DeviceScope(int device_id) : want(device_id) {
-        if (hipGetDevice(&prev) != hipSuccess) ok = false;
-        else if (prev != want && hipSetDevice(want) != hipSuccess) ok = false;
-    }
-    ~DeviceScope() {
-        if (ok && prev != want) (void)hipSetDevice(prev);
-    }
-};
-
 #endif
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -70,6 +58,32 @@ __device__ __forceinline__ bf16x8_t as_bf16x8(u32x4_t v) { return __builtin_bit_
 
 __host__ __device__ inline int pol_h0_bytes(int G) { return G * G * 32; }
 __host__ __device__ inline int pol_h1_bytes(int G) { return (((G - 2) * (G - 2) + 15) / 16) * 16 * 32; }
+
+// ---- dynamic LDS of the kernels whose layout is more than h0 ++ h1: ONE definition, used by the kernel's carve-up (which
+// static_asserts it against the layout constants it indexes with) and by the host for the launch's byte count.
+// k_policy_front_wgrad<GO, CO, ..>: per wave the gradient image A [RA rows][16 columns][CO channels] and the activation image
+// B [RA + 2 rows][18 columns][16 channels], bf16; afterwards the block's reduction scratch float [wave][9 taps][CO][16] over them
+__host__ __device__ constexpr int pol_wgrad_rows(int GO) { return GO + 1 + (GO & 1 ? 0 : 1); }  // GO + at least one zero row, an even count
+__host__ __device__ constexpr int pol_wgrad_wave_bytes(int GO, int CO) { return pol_wgrad_rows(GO) * 16 * CO * 2 + (pol_wgrad_rows(GO) + 2) * 18 * 32; }
+__host__ __device__ constexpr int pol_wgrad_block_bytes(int GO, int CO, int wpb) {
+    return wpb * pol_wgrad_wave_bytes(GO, CO) > wpb * 9 * CO * 16 * 4 ? wpb * pol_wgrad_wave_bytes(GO, CO) : wpb * 9 * CO * 16 * 4;
+}
+// k_policy_front_dgrad<G, W2>: per wave the zero-padded dz2 image (4 octet arrays of G rows) and both channel halves of the h1 image
+// (W2, the fused weight gradient: rows of 18 cells and the rows its position contraction reads); W2: afterwards the block's reduction
+// scratch float [wave][9 taps][32][16] over them
+__host__ __device__ constexpr int pol_dgrad_wave_bytes(int G, bool W2) {
+    return W2 ? 4 * G * 18 * 16 + 2 * (pol_wgrad_rows(G - 4) + 2) * 18 * 16 : 4 * G * G * 16 + 2 * ((((G - 2) * (G - 2) + 15) >> 4) << 4) * 16;
+}
+__host__ __device__ constexpr int pol_dgrad_block_bytes(int G, bool W2, int wpb) {
+    return W2 && wpb * pol_dgrad_wave_bytes(G, W2) < wpb * 9 * 32 * 16 * 4 ? wpb * 9 * 32 * 16 * 4 : wpb * pol_dgrad_wave_bytes(G, W2);
+}
+// k_policy_features_fact<G>: per wave h0 with h2s over it (72 bytes per position: FACT_H2R), then h1 ++ the four agents' conv1 patches
+// with the four staged patch rows (25 positions + 64 bytes of metadata each) over them
+#define FACT_H2R 72
+__host__ __device__ constexpr int pol_fact_wave_bytes(int G) {
+    const int pp = (((G - 4) * (G - 4) + 31) >> 5) << 5, h1hp = (((G - 2) * (G - 2) + 15) / 16) * 16 * 32 + 4 * 9 * 32, pst = 4 * (25 * FACT_H2R + 64);
+    return (G * G * 32 > pp * FACT_H2R ? G * G * 32 : pp * FACT_H2R) + (h1hp > pst ? h1hp : pst);
+}
 
 // One lane's code bytes of a sample (cells lane, lane + 64, ...: at most 4 when G*G <= 256).  Kept as separate
 // registers until they are used, so that the loads can stay in flight for a whole sample.
@@ -277,20 +291,3 @@ __device__ __forceinline__ void head_stages_bcde(const HeadArgs& a, uint8_t* xs,
         }
     }
 }
-
-
-// Deterministic mode (ctf_policy_set_deterministic, include/ctf_policy.h): with a workspace registered for the device, the weight /
-// bias gradient kernels do not end in float atomics on the gradient (whose order of arrival differs from run to run) — every block
-// stores its partial sums in its own slice of the workspace and a second launch adds the slices IN BLOCK ORDER.
-struct DetWorkspace {
-    float* ptr;      // NULL: off (atomics)
-    int64_t floats;
-};
-__attribute__((visibility("hidden"))) DetWorkspace ctf_policy_det(int device_id);
-// dst[i] += sum over b = 0 .. n_blocks - 1 (in that order, four interleaved chains) of part[b * stride + i], i < elems
-__attribute__((visibility("hidden"))) hipError_t ctf_policy_det_reduce(const float* part, int n_blocks, int64_t stride, int elems, float* dst,
-                                                                      hipStream_t st);
-
-// host-side helpers defined in ctf_policy.hip
-__attribute__((visibility("hidden"))) int ctf_policy_fail(const char* msg);      // sets ctf_policy_last_error(), returns -1
-__attribute__((visibility("hidden"))) int ctf_policy_cus(int device_id);          // compute units of a device (cached), 0 on error

@@ -19,7 +19,7 @@
 //                                   y1[agent] = bf16(D + (W_flat . h2_v)[env] + b) — the pre-activation ctf_policy_head consumes
 //
 // The view GEMM itself ([E][32 * PP] x [32 * PP][256], fp32 out) is the BLAS library's (policy_native.py).
-#include "ctf_policy_dev.h"
+#include "ctf_policy_host.h"
 
 #define FACT_MT 128      // slots per tile
 #define FACT_BINS 256    // own cells (G * G <= 256)
@@ -197,13 +197,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     const int wpb = blockDim.x / WAVE;
     const int KRB = fa.KR * 2;  // bytes of a patch row
-    constexpr int H2R = 72;  // bytes per position of h2s and of a staged patch row: 64 + 8, so that 16 lanes' 8-byte pieces cover all banks once
+    constexpr int H2R = FACT_H2R;  // bytes per position of h2s and of a staged patch row: 64 + 8, so that 16 lanes' 8-byte pieces cover all banks once
     constexpr int PSTB = 25 * H2R + 64;  // a staged row: 25 positions, then the 32 metadata / padding elements
     constexpr int H2S = PP * H2R, HPB = 9 * 32;
     constexpr int H1B = (((G - 2) * (G - 2) + 15) / 16) * 16 * 32;
     constexpr int STAGE_REGION = (H1B + 4 * HPB) > 4 * PSTB ? (H1B + 4 * HPB) : 4 * PSTB;  // h1 ++ hp, later the staged patch rows
     constexpr int H0H2 = G * G * 32 > H2S ? G * G * 32 : H2S;  // h0, then (once the last conv1 operand has been read) h2s over it
-    constexpr int PER_WAVE = H0H2 + STAGE_REGION;
+    constexpr int PER_WAVE = pol_fact_wave_bytes(TG);
+    static_assert(PER_WAVE == H0H2 + STAGE_REGION, "the layout constants and the launch's LDS size agree");
     uint8_t* h0 = (uint8_t*)lds + wave * PER_WAVE;
     uint8_t* h2s = h0;                    // bf16 [PP positions][32 channels]: tanh(conv2) of the shared view — written over h0, which is
                                           // rebuilt from the code bytes for every env (two waves per SIMD are worth more than the
@@ -746,17 +747,6 @@ extern "C" int32_t ctf_policy_fact_max_tiles(int32_t n_envs, int32_t n_sel, int3
     return (int32_t)(((int64_t)n_envs * n_sel + FACT_MT - 1) / FACT_MT + grid_size * grid_size);
 }
 
-static int pack_sel(const int32_t* agent_sel, int n_sel, int n_agents, uint64_t* out) {
-    if (!agent_sel || n_sel < 1 || n_sel > 4) return ctf_policy_fail("the factored path takes 1..4 selected agents");
-    uint64_t p = 0;
-    for (int k = 0; k < n_sel; k++) {
-        if (agent_sel[k] < 0 || agent_sel[k] >= n_agents) return ctf_policy_fail("agent_sel entry out of range");
-        p |= (uint64_t)agent_sel[k] << (4 * k);
-    }
-    *out = p;
-    return 0;
-}
-
 extern "C" int ctf_policy_fact_bucket(const uint16_t* selfcell_dev, int32_t n_envs, int32_t n_agents, int32_t grid_size,
                                       const int32_t* agent_sel, int32_t n_sel, int32_t* work_dev, int32_t* slot_of_dev,
                                       int32_t* row_of_slot_dev, int32_t device_id, void* stream) {
@@ -764,7 +754,7 @@ extern "C" int ctf_policy_fact_bucket(const uint16_t* selfcell_dev, int32_t n_en
     if (grid_size * grid_size > FACT_BINS) return ctf_policy_fail("grid_size * grid_size must be <= 256");
     if (n_envs < 1 || n_agents < 1 || n_agents > 16 || (int64_t)n_envs * n_sel > 0x7FFFFFF0) return ctf_policy_fail("n_envs / n_agents out of range");
     BucketArgs a;
-    if (pack_sel(agent_sel, n_sel, n_agents, &a.sel_pack)) return -1;
+    if (pol_pack_sel(agent_sel, n_sel, n_agents, 4, &a.sel_pack)) return -1;
     a.selfcells = selfcell_dev;
     a.hist = work_dev;
     a.cursor = work_dev + FACT_BINS;
@@ -775,16 +765,14 @@ extern "C" int ctf_policy_fact_bucket(const uint16_t* selfcell_dev, int32_t n_en
     a.E = n_envs; a.N = n_agents; a.A = n_sel; a.GG = grid_size * grid_size;
     a.t_max = ctf_policy_fact_max_tiles(n_envs, n_sel, grid_size);
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
+    if (scope.error) return ctf_policy_fail(scope.error);
     hipStream_t st = (hipStream_t)stream;
     const int total = n_envs * n_sel;
     const int blocks = (total + 256 * FACT_ITEMS_PER_THREAD - 1) / (256 * FACT_ITEMS_PER_THREAD);
     hipLaunchKernelGGL(k_fact_hist, dim3(blocks), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_fact_scan, dim3(1), dim3(FACT_BINS), 0, st, a);
     hipLaunchKernelGGL(k_fact_assign, dim3(blocks), dim3(256), 0, st, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(hipGetLastError());
 }
 
 extern "C" int ctf_policy_features_fact(const uint8_t* codes_dev, const uint16_t* meta_dev, const uint16_t* selfcell_dev, int32_t n_envs,
@@ -800,55 +788,27 @@ extern "C" int ctf_policy_features_fact(const uint8_t* codes_dev, const uint16_t
     if (n_envs < 1 || n_agents < 1 || n_agents > 16) return ctf_policy_fail("n_envs / n_agents out of range");
     if (((uintptr_t)view_dev & 15) || ((uintptr_t)prow_dev & 15) || ((uintptr_t)meta_dev & 3)) return ctf_policy_fail("view / prow must be 16-byte, meta 4-byte aligned");
     PolicyArgs& a = fa.p;
-    if (pack_sel(agent_sel, n_sel, n_agents, &a.sel_pack)) return -1;
+    if (pol_pack_sel(agent_sel, n_sel, n_agents, 4, &a.sel_pack)) return -1;
     a.codes = codes_dev; a.meta = meta_dev; a.act = nullptr;
     a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
     a.w2frag = (const u32x4_t*)conv2_frag_dev; a.b2 = conv2_bias_dev;
     a.n_envs = n_envs; a.N = n_agents; a.G = grid_size; a.M = meta_len; a.n_sel = n_sel; a.Kp = 0;
     a.h0_out = nullptr; a.h1_out = nullptr;
-    const int G1 = grid_size - 2, G2 = grid_size - 4;
-    a.inv_g1 = (65536 + G1 - 1) / G1;
-    a.inv_g2 = (65536 + G2 - 1) / G2;
-    for (int p = 0; p < G1 * G1; p++)
-        if ((int)(((uint32_t)p * a.inv_g1) >> 16) != p / G1) return ctf_policy_fail("internal: reciprocal of G-2 not exact");
-    for (int p = 0; p < G2 * G2; p++)
-        if ((int)(((uint32_t)p * a.inv_g2) >> 16) != p / G2) return ctf_policy_fail("internal: reciprocal of G-4 not exact");
+    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
     fa.selfcells = selfcell_dev; fa.slot_of = slot_of_dev; fa.view = view_dev; fa.prow = prow_dev; fa.A = n_sel;
     const int n_cus = ctf_policy_cus(device_id);
     if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
-    const int pp = fa.KV / 32;
-    const int h1hp = pol_h1_bytes(grid_size) + 4 * 9 * 32;
-    const int pstb = 25 * 72 + 64;  // k_policy_features_fact's PSTB / H2R
-    const int h0h2 = pol_h0_bytes(grid_size) > pp * 72 ? pol_h0_bytes(grid_size) : pp * 72;  // k_policy_features_fact's H0H2
-    const int per_wave = h0h2 + (h1hp > 4 * pstb ? h1hp : 4 * pstb);
-    int wpb = 4;  // two blocks of four waves per CU = two waves per SIMD (16.7 KB of LDS per wave since h2s lies over h0)
-    if (const char* ov = getenv("CTF_POLICY_FACT_WPB")) {  // profiling only
-        const int v = atoi(ov);
-        if (v >= 1 && v <= 4) wpb = v;
-    }
-    const size_t sh = (size_t)wpb * per_wave;
+    if (scope.error) return ctf_policy_fail(scope.error);
+    // two blocks of four waves per CU = two waves per SIMD (16.7 KB of LDS per wave since h2s lies over h0)
+    const int wpb = pol_env_int("CTF_POLICY_FACT_WPB", 1, 4, 4);  // profiling only
+    const size_t sh = (size_t)wpb * pol_fact_wave_bytes(grid_size);
     int per_cu = (int)((160 * 1024) / sh);
     if (per_cu < 1) per_cu = 1;
-    if (const char* ov = getenv("CTF_POLICY_FACT_BLOCKS_PER_CU")) {  // profiling only
-        const int v = atoi(ov);
-        if (v >= 1 && v < per_cu) per_cu = v;
-    }
+    per_cu = pol_env_int("CTF_POLICY_FACT_BLOCKS_PER_CU", 1, per_cu, per_cu);  // profiling only
     int blocks = (n_envs + wpb - 1) / wpb;
     if (blocks > n_cus * per_cu) blocks = n_cus * per_cu;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t err = hipSuccess;
-    if (grid_size == 15) {
-        err = hipFuncSetAttribute((const void*)k_policy_features_fact<15>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features_fact<15>, dim3(blocks), dim3(wpb * WAVE), sh, st, fa);
-    } else {
-        err = hipFuncSetAttribute((const void*)k_policy_features_fact<11>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(k_policy_features_fact<11>, dim3(blocks), dim3(wpb * WAVE), sh, st, fa);
-    }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(pol_launch(grid_size == 15 ? k_policy_features_fact<15> : k_policy_features_fact<11>, blocks, wpb * WAVE, sh, (hipStream_t)stream, fa));
 }
 
 extern "C" int ctf_policy_fc1_patch(const uint16_t* prow_dev, const int32_t* row_of_slot_dev, const int32_t* work_dev, const float* yview_dev,
@@ -867,14 +827,9 @@ extern "C" int ctf_policy_fc1_patch(const uint16_t* prow_dev, const int32_t* row
     a.E = n_envs; a.KR = kr;
     const int t_max = ctf_policy_fact_max_tiles(n_envs, n_sel, grid_size);
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
+    if (scope.error) return ctf_policy_fail(scope.error);
     const int sh = 2 * FACT_MT * (128 + FACT_ROW_PAD);
-    if (grid_size == 15) hipLaunchKernelGGL((k_policy_fc1_patch<15, false>), dim3(t_max), dim3(256), sh, st, a);
-    else hipLaunchKernelGGL((k_policy_fc1_patch<11, false>), dim3(t_max), dim3(256), sh, st, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(pol_launch(grid_size == 15 ? k_policy_fc1_patch<15, false> : k_policy_fc1_patch<11, false>, t_max, 256, sh, (hipStream_t)stream, a));
 }
 
 extern "C" int ctf_policy_fc1_patch_head(const uint16_t* prow_dev, const int32_t* row_of_slot_dev, const int32_t* work_dev, const float* yview_dev,
@@ -904,20 +859,9 @@ extern "C" int ctf_policy_fc1_patch_head(const uint16_t* prow_dev, const int32_t
     h.entropy = entropy_dev; h.value = value_dev; h.logits = logits_dev; h.B = (int64_t)n_envs * n_sel; h.A = n_actions; h.seed = seed; h.offset = offset;
     const int t_max = ctf_policy_fact_max_tiles(n_envs, n_sel, grid_size);
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
+    if (scope.error) return ctf_policy_fail(scope.error);
     const int sh = 2 * FACT_MT * (128 + FACT_ROW_PAD) + HEAD_TILE * HEAD_XS_ROW;
-    hipError_t err;
-    if (grid_size == 15) {
-        err = hipFuncSetAttribute((const void*)k_policy_fc1_patch<15, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_fc1_patch<15, true>), dim3(t_max), dim3(256), sh, st, a);
-    } else {
-        err = hipFuncSetAttribute((const void*)k_policy_fc1_patch<11, true>, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-        if (err == hipSuccess) hipLaunchKernelGGL((k_policy_fc1_patch<11, true>), dim3(t_max), dim3(256), sh, st, a);
-    }
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(pol_launch(grid_size == 15 ? k_policy_fc1_patch<15, true> : k_policy_fc1_patch<11, true>, t_max, 256, sh, (hipStream_t)stream, a));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1038,11 +982,6 @@ extern "C" int ctf_policy_view_gemm(const uint16_t* view_dev, const uint16_t* w_
     ViewGemmArgs g;
     g.a = view_dev; g.w = w_rows_dev; g.out = yview_dev; g.M = n_rows; g.K = kv;
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
-    const int sh = 3 * VG_STAGE;
-    hipError_t err = hipFuncSetAttribute((const void*)k_view_gemm, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-    if (err == hipSuccess) hipLaunchKernelGGL(k_view_gemm, dim3((n_rows + 127) / 128), dim3(512), sh, (hipStream_t)stream, g);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    if (scope.error) return ctf_policy_fail(scope.error);
+    return pol_finish(pol_launch(k_view_gemm, (n_rows + 127) / 128, 512, 3 * VG_STAGE, (hipStream_t)stream, g));
 }

@@ -9,7 +9,7 @@
 // layer, HBM-bound (it reads dy and x once).  The contraction runs over SAMPLES, so both MFMA operands must be sample-contiguous per
 // lane — transposed against the row-major tensors; the tiles are staged in LDS as they are and read through ds_read_b64_tr_b16 (the
 // weight-gradient kernels of the conv front do the same over positions, ctf_policy.hip).
-#include "ctf_policy_dev.h"
+#include "ctf_policy_host.h"
 
 typedef short tail_i16x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4_t tail_tr_operand(const uint8_t* lds_addr, int second_block_bytes) {
@@ -173,9 +173,8 @@ extern "C" int ctf_policy_linear_wgrad(const uint16_t* dy_dev, const uint16_t* x
     if (!n_samples) return 0;
     const int n_cus = ctf_policy_cus(device_id);
     if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return ctf_policy_fail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return ctf_policy_fail("hipSetDevice failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     TailWgradArgs a;
     a.dy = dy_dev; a.x = x_dev; a.dw = dw_dev; a.db = db_dev; a.M = n_samples;
     a.x_stride = n_in; a.dw_stride = n_in; a.k_base = 0; a.n_slabs = 1;
@@ -189,8 +188,7 @@ extern "C" int ctf_policy_linear_wgrad(const uint16_t* dy_dev, const uint16_t* x
         a.part = det.ptr;
         a.part_stride = (int64_t)n * k + n;
         if (a.part && blocks * a.part_stride > det.floats) { too_small = true; return; }
-        if (err == hipSuccess && sh > 48 * 1024) err = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-        if (err == hipSuccess) hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), sh, st, a);
+        if (err == hipSuccess) err = pol_launch(kernel, blocks, 256, sh, st, a);
         if (err == hipSuccess && a.part) {  // the blocks' tiles -> dw (and db), in block order
             const int ranges = (int)(blocks / a.n_slabs);
             hipLaunchKernelGGL(k_tail_det_reduce, dim3((unsigned)((a.n_slabs * n * k + 255) / 256)), dim3(256), 0, st, (const float*)a.part, a.part_stride,
@@ -217,11 +215,9 @@ extern "C" int ctf_policy_linear_wgrad(const uint16_t* dy_dev, const uint16_t* x
         }
     } else err = hipErrorInvalidValue;
     if (err == hipSuccess) err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (too_small) return ctf_policy_fail("deterministic mode: the registered workspace is too small for this launch (ctf_policy_set_deterministic)");
+    if (too_small) return pol_finish(POL_WORKSPACE_TOO_SMALL);
     if (err == hipErrorInvalidValue) return ctf_policy_fail("ctf_policy_linear_wgrad is built for (n_out, n_in) = (128, 256), (16, 128) and (256, a multiple of 64 without bias)");
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(err);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -313,16 +309,12 @@ extern "C" int ctf_rollout_store_step(const uint8_t* codes_dev, const uint16_t* 
     }
     const int n_cus = ctf_policy_cus(device_id);
     if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
-    int dev_prev = 0;
-    if (hipGetDevice(&dev_prev) != hipSuccess) return ctf_policy_fail("hipGetDevice failed");
-    if (dev_prev != device_id && hipSetDevice(device_id) != hipSuccess) return ctf_policy_fail("hipSetDevice failed");
+    DeviceScope scope(device_id);
+    if (scope.error) return ctf_policy_fail(scope.error);
     int64_t blocks = ((int64_t)n_trained * n_envs + 3) / 4;
     if (blocks > (int64_t)n_cus * 16) blocks = (int64_t)n_cus * 16;
     hipLaunchKernelGGL(k_rollout_store, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t err = hipGetLastError();
-    if (dev_prev != device_id) (void)hipSetDevice(dev_prev);
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    return pol_finish(hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -449,11 +441,6 @@ extern "C" int ctf_policy_fc1_dgrad(const uint16_t* dy_dev, const uint16_t* wt_d
     Fc1DgradArgs g;
     g.dy = dy_dev; g.wt = wt_dev; g.out = d_act_dev; g.M = n_samples; g.Kp = kp;
     DeviceScope scope(device_id);
-    if (!scope.ok) return ctf_policy_fail("hipSetDevice failed");
-    const int sh = 3 * FD_STAGE + 8 * 32 * FD_OROW;
-    hipError_t err = hipFuncSetAttribute((const void*)k_fc1_dgrad, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-    if (err == hipSuccess) hipLaunchKernelGGL(k_fc1_dgrad, dim3((n_samples + 255) / 256), dim3(512), sh, (hipStream_t)stream, g);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err != hipSuccess) return ctf_policy_fail(hipGetErrorString(err));
-    return 0;
+    if (scope.error) return ctf_policy_fail(scope.error);
+    return pol_finish(pol_launch(k_fc1_dgrad, (n_samples + 255) / 256, 512, 3 * FD_STAGE + 8 * 32 * FD_OROW, (hipStream_t)stream, g));
 }

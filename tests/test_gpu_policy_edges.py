@@ -404,3 +404,67 @@ def test_rollout_store_step_rejects_bad_arguments_and_writes_nothing():
         assert rc != 0 and last_error(lib) != "", what
         for k, v in out.items():
             assert bool((v == GUARD).all()), (what, k)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# D. the caller's current device is the caller's: an entry point of each source file, called for device 1 while device 0 is current
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_entry_points_leave_the_callers_device_current_on_success_and_on_failure():
+    """ctf_policy_features, ctf_policy_fact_bucket and ctf_policy_linear_wgrad with device_id = 1, inputs and stream of device 1, while
+    device 0 is current: device 0 is still current afterwards, the outputs equal bit for bit those of the same calls made with device 1
+    current, and calls that fail (a null pointer, an agent_sel entry out of range, a layer shape the kernel is not built for — the last
+    one is refused only after the device switch) leave device 0 current too, return non-zero and set ctf_policy_last_error()."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    lib = abi.load_library()
+    d1 = torch.device("cuda", 1)
+    g, c, m, E, N = 11, 8, 14, 2, 4  # two envs, two agents per team
+    rng = np.random.default_rng(11)
+    codes = torch.tensor((rng.integers(0, c, (E, N, g, g)) * (rng.random((E, N, g, g)) < 0.3)).astype(np.uint8), device=d1)
+    meta = torch.tensor(rng.random((E, N, m)).astype(np.float16), device=d1)
+    cells = torch.tensor(rng.integers(0, g * g, (E, N)).astype(np.int16), device=d1)
+    p = fill_(native.CtfPolicyNative(9, c, g, m)).to(d1)._ready()
+    tiles = lib.ctf_policy_fact_max_tiles(E, 2, g)
+    rows = 70  # two blocks of the heads' kernel at most: a sum of two atomic addends onto zero has one value in either order
+    dy = torch.tensor(rng.standard_normal((rows, 16)), dtype=BF, device=d1)
+    x = torch.tensor(rng.standard_normal((rows, 128)), dtype=BF, device=d1)
+    st1 = C.c_void_p(torch.cuda.current_stream(d1).cuda_stream)
+    sel_ok, sel_bad = (C.c_int32 * 2)(0, 1), (C.c_int32 * 2)(0, N)
+
+    def features(codes_=codes, sel=sel_ok):
+        act = torch.zeros((2 * E, p["kp"]), dtype=BF, device=d1)
+        rc = lib.ctf_policy_features(ptr(codes_), ptr(meta), E, N, g, m, sel, 2, ptr(p["f1"]), ptr(p["b1"]), ptr(p["f2"]), ptr(p["b2"]), ptr(act),
+                                     None, 1, st1)
+        return rc, [act]
+
+    def bucket(cells_=cells, sel=sel_ok):
+        i32 = dict(dtype=torch.int32, device=d1)
+        outs = [torch.zeros(576 + tiles, **i32), torch.zeros(2 * E, **i32), torch.zeros(tiles * 128, **i32)]
+        rc = lib.ctf_policy_fact_bucket(ptr(cells_), E, N, g, sel, 2, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), 1, st1)
+        return rc, outs
+
+    def linear(dy_=dy, n_in=128):
+        dw, db = torch.zeros((16, 128), dtype=torch.float32, device=d1), torch.zeros(16, dtype=torch.float32, device=d1)
+        rc = lib.ctf_policy_linear_wgrad(ptr(dy_), ptr(x), rows, 16, n_in, ptr(dw), ptr(db), 1, st1)
+        return rc, [dw, db]
+
+    def run(call, **kw):
+        rc, outs = call(**kw)
+        torch.cuda.synchronize(d1)
+        return rc, outs
+
+    with torch.cuda.device(1):
+        want = {call: run(call) for call in (features, bucket, linear)}
+    torch.cuda.set_device(0)
+    for call, (rc_want, outs_want) in want.items():
+        assert rc_want == 0, (call.__name__, last_error(lib))
+        rc, outs = run(call)
+        assert rc == 0, (call.__name__, last_error(lib))
+        assert torch.cuda.current_device() == 0, call.__name__
+        assert all(torch.equal(a, b) for a, b in zip(outs, outs_want)), call.__name__
+    bad = [(features, dict(codes_=None)), (features, dict(sel=sel_bad)), (bucket, dict(cells_=None)), (bucket, dict(sel=sel_bad)),
+           (linear, dict(dy_=None)), (linear, dict(n_in=64))]
+    for call, kw in bad:
+        rc, _ = run(call, **kw)
+        assert torch.cuda.current_device() == 0, (call.__name__, kw.keys())
+        assert rc != 0 and last_error(lib) != "", (call.__name__, kw.keys())
