@@ -235,3 +235,26 @@ def check(rc, lib=None):
         lib = lib or load_library()
         msg = lib.ctf_last_error()
         raise CtfLibraryError(f"ctf call failed ({rc}): {msg.decode() if msg else ''}")
+
+
+# -- the one place the package calls a status-returning entry point ---------------------------------
+def ptr(t):
+    """A tensor's device address as a pointer argument (every ``_P`` of SYMBOLS converts a plain int); None stays None = NULL."""
+    return None if t is None else t.data_ptr()
+
+
+def stream_ptr(device):
+    """torch's current stream of ``device`` as the ABI's stream argument."""
+    import torch
+
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(lib, name, *args):
+    """``lib.<name>(*args)``; a non-zero status raises CtfLibraryError with the text of the error getter of that entry point's
+    header: include/ctf_policy.h (ctf_policy_*, ctf_rollout_*) or include/ctf_env.h (every other name)."""
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        if name.startswith(("ctf_policy_", "ctf_rollout_")):
+            raise CtfLibraryError(name + ": " + (lib.ctf_policy_last_error() or b"").decode())
+        check(rc, lib)

@@ -92,7 +92,7 @@ class VecGridworldCtf:
         with torch.cuda.device(self.device):
             torch.cuda.current_stream()  # make sure torch has initialised HIP on this device first
             h = C.c_void_p()
-            _abi.check(self._lib.ctf_create(C.byref(self.cfg), self.n_envs, self.device.index, C.byref(h)), self._lib)
+            _abi.call(self._lib, "ctf_create", C.byref(self.cfg), self.n_envs, self.device.index, C.byref(h))
         self._h = h
         E, N = self.n_envs, self.N_AGENTS
         self.rewards = torch.zeros((E, N), dtype=torch.float32, device=self.device)
@@ -217,7 +217,14 @@ class VecGridworldCtf:
 
     # -- plumbing -----------------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+        return _abi.stream_ptr(self.device)
+
+    def _call(self, name, *args):
+        """One status-returning entry point of include/ctf_env.h on this object's handle (a failure raises CtfLibraryError)."""
+        _abi.call(self._lib, name, self._h, *args)
+
+    def _reverse_bits(self, reverse_mask):
+        return _abi.REVERSE_DEFAULT if reverse_mask is None else int(reverse_mask) & ((1 << self.N_AGENTS) - 1)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -235,7 +242,7 @@ class VecGridworldCtf:
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dtype
                 and t.is_contiguous() and t.numel() == numel):
             raise ValueError(f"expected a contiguous {dtype} tensor of {numel} elements on {self.device}")
-        return C.c_void_p(t.data_ptr())
+        return _abi.ptr(t)
 
     # -- RNG ----------------------------------------------------------------------------------
     def seed(self, py_seeds=None, np_seeds=None):
@@ -243,25 +250,26 @@ class VecGridworldCtf:
         npz = _as_seed_array(np_seeds if np_seeds is not None else py_seeds, self.n_envs)
         if self.rng_mode == "mt19937" and (npz >> np.uint64(32)).any():
             raise ValueError("Seed must be between 0 and 2**32 - 1")  # np.random.seed's own message
-        _abi.check(self._lib.ctf_seed(self._h, py.ctypes.data_as(C.c_void_p), npz.ctypes.data_as(C.c_void_p), self._stream()), self._lib)
+        self._call("ctf_seed", py.ctypes.data_as(C.c_void_p), npz.ctypes.data_as(C.c_void_p), self._stream())
         _torch().cuda.current_stream(self.device).synchronize()  # host seed arrays may go away
 
     def set_rng_state(self, env_index, py_mt625=None, np_mt625=None):
         a = None if py_mt625 is None else np.ascontiguousarray(py_mt625, dtype=np.uint32)
         b = None if np_mt625 is None else np.ascontiguousarray(np_mt625, dtype=np.uint32)
-        _abi.check(self._lib.ctf_set_rng_state(self._h, env_index, None if a is None else a.ctypes.data_as(C.c_void_p),
-                                               None if b is None else b.ctypes.data_as(C.c_void_p)), self._lib)
+        self._call("ctf_set_rng_state", env_index, None if a is None else a.ctypes.data_as(C.c_void_p),
+                   None if b is None else b.ctypes.data_as(C.c_void_p))
 
     def get_rng_state(self, env_index):
         a, b = np.zeros(625, np.uint32), np.zeros(625, np.uint32)
-        _abi.check(self._lib.ctf_get_rng_state(self._h, env_index, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)), self._lib)
+        self._call("ctf_get_rng_state", env_index, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p))
         return a, b
 
     def set_rng_states(self, py_states=None, np_states=None):
         """Bulk, stream-ordered hand-over: uint32 CUDA tensors [E, 625] (624 words + position per env), either may be None."""
         torch = _torch()
-        ptr = lambda t: None if t is None else self._check_dev(t, torch.int32 if t.dtype == torch.int32 else torch.uint32, self.n_envs * 625)
-        _abi.check(self._lib.ctf_set_rng_states(self._h, ptr(py_states), ptr(np_states), self._stream()), self._lib)
+        py, np_ = (None if t is None else self._check_dev(t, torch.int32 if t.dtype == torch.int32 else torch.uint32, self.n_envs * 625)
+                   for t in (py_states, np_states))
+        self._call("ctf_set_rng_states", py, np_, self._stream())
 
     def get_rng_states(self, py=True, np_=True):
         """-> (py_states, np_states): int32 CUDA tensors [E, 625] holding the uint32 words of both generators of every env in
@@ -269,68 +277,62 @@ class VecGridworldCtf:
         torch = _torch()
         a = torch.empty((self.n_envs, 625), dtype=torch.int32, device=self.device) if py else None
         b = torch.empty((self.n_envs, 625), dtype=torch.int32, device=self.device) if np_ else None
-        _abi.check(self._lib.ctf_get_rng_states(self._h, None if a is None else C.c_void_p(a.data_ptr()),
-                                                None if b is None else C.c_void_p(b.data_ptr()), self._stream()), self._lib)
+        self._call("ctf_get_rng_states", _abi.ptr(a), _abi.ptr(b), self._stream())
         return a, b
 
     def get_rng_counters(self):
         """counter mode: int64 CUDA tensor [E, 2] = words consumed so far from the `random` / np.random stream of every env (the
         whole RNG state of an env there, besides its two seeds).  Stream-ordered."""
         out = _torch().empty((self.n_envs, 2), dtype=_torch().int64, device=self.device)
-        _abi.check(self._lib.ctf_get_rng_counters(self._h, C.c_void_p(out.data_ptr()), self._stream()), self._lib)
+        self._call("ctf_get_rng_counters", _abi.ptr(out), self._stream())
         return out
 
     def set_rng_counters(self, counters):
         """counter mode: the way back (int64 CUDA tensor [E, 2]) — a checkpoint restore after ``seed``."""
-        ptr = self._check_dev(counters, _torch().int64, self.n_envs * 2)
-        _abi.check(self._lib.ctf_set_rng_counters(self._h, ptr, self._stream()), self._lib)
+        self._call("ctf_set_rng_counters", self._check_dev(counters, _torch().int64, self.n_envs * 2), self._stream())
 
     # -- the hot path -------------------------------------------------------------------------
     def reset(self, mask=None):
         ptr = None if mask is None else self._check_dev(mask, _torch().uint8, self.n_envs)
-        _abi.check(self._lib.ctf_reset(self._h, ptr, self._stream()), self._lib)
+        self._call("ctf_reset", ptr, self._stream())
 
     def step(self, actions, auto_reset=False, want_f64=False):
         """actions: int8 CUDA tensor [E, N].  -> (rewards float32 [E, N], done uint8 [E]) (views of
         this object's buffers).  With want_f64 the float64 rewards are also written to ``rewards64``."""
         a = self._check_dev(actions, _torch().int8, self.n_envs * self.N_AGENTS)
-        _abi.check(self._lib.ctf_step(self._h, a, C.c_void_p(self.rewards.data_ptr()),
-                                      C.c_void_p(self.rewards64.data_ptr()) if want_f64 else None,
-                                      C.c_void_p(self.done.data_ptr()), _abi.STEP_AUTO_RESET if auto_reset else 0,
-                                      self._stream()), self._lib)
+        self._call("ctf_step", a, _abi.ptr(self.rewards), _abi.ptr(self.rewards64 if want_f64 else None), _abi.ptr(self.done),
+                   _abi.STEP_AUTO_RESET if auto_reset else 0, self._stream())
         return self.rewards, self.done
 
     def observe(self, reverse_mask=None, obs=True, meta=True):
         """-> (obs uint8 [E, N, C, G, G], meta float16 [E, N, 2N+6]).  ``reverse_mask`` bit i = reverse_grid
         for agent i (default: team(i) == 1, what every caller in the reference passes)."""
-        rm = _abi.REVERSE_DEFAULT if reverse_mask is None else int(reverse_mask) & ((1 << self.N_AGENTS) - 1)
-        _abi.check(self._lib.ctf_observe(self._h, C.c_void_p(self.obs.data_ptr()) if obs else None,
-                                         C.c_void_p(self.meta.data_ptr()) if meta else None, rm, self._stream()), self._lib)
+        self._call("ctf_observe", _abi.ptr(self.obs if obs else None), _abi.ptr(self.meta if meta else None),
+                   self._reverse_bits(reverse_mask), self._stream())
         return self.obs, self.meta
 
     def observe_kernel(self):
         """Which kernel ``observe`` launches for this object's buffer: "k_observe_tiles" or "k_observe" (the library's own rule)."""
-        return "k_observe_tiles" if self._lib.ctf_observe_kernel(self._h, C.c_void_p(self.obs.data_ptr())) == 1 else "k_observe"
+        return "k_observe_tiles" if self._lib.ctf_observe_kernel(self._h, _abi.ptr(self.obs)) == 1 else "k_observe"
 
     def step_observe_launches(self):
         """Launches ``step_observe`` makes into this object's buffer: 1 (k_step_observe) or 2 (step, then observe)."""
-        return int(self._lib.ctf_step_observe_launches(self._h, C.c_void_p(self.obs.data_ptr())))
+        return int(self._lib.ctf_step_observe_launches(self._h, _abi.ptr(self.obs)))
 
     def observe_stores(self):
         """"nontemporal" when ``observe`` streams this object's buffer past the caches (the tile kernel on a batch whose observations
         exceed 320 MB), else "plain"."""
-        return "nontemporal" if self._lib.ctf_observe_stores_hinted(self._h, C.c_void_p(self.obs.data_ptr())) == 1 else "plain"
+        return "nontemporal" if self._lib.ctf_observe_stores_hinted(self._h, _abi.ptr(self.obs)) == 1 else "plain"
 
     def observe_codes(self, reverse_mask=None, codes=True, meta=True):
         """The observation in compact form -> (codes uint8 [E, N, G, G], meta float16 [E, N, 2N+6]): low 7 bits = the tile
         plane (1..C-1) that is 1 at the cell, 0 = none; bit 7 = plane 0 (own position).  ``expand_codes`` gives the planes.
         ``self.self_cells`` (uint16 [E, N]) receives the cell index of every agent's bit 7 in the same launch."""
-        rm = _abi.REVERSE_DEFAULT if reverse_mask is None else int(reverse_mask) & ((1 << self.N_AGENTS) - 1)
+        rm = self._reverse_bits(reverse_mask)
         if self._self_cells is None:
             self._self_cells = _torch().zeros((self.n_envs, self.N_AGENTS), dtype=_torch().int16, device=self.device)
-        _abi.check(self._lib.ctf_observe_codes(self._h, C.c_void_p(self.codes.data_ptr()) if codes else None,
-                                               C.c_void_p(self.meta.data_ptr()) if meta else None,
-                                               C.c_void_p(self._self_cells.data_ptr()) if codes else None, rm, self._stream()), self._lib)
+        self._call("ctf_observe_codes", _abi.ptr(self.codes if codes else None), _abi.ptr(self.meta if meta else None),
+                   _abi.ptr(self._self_cells if codes else None), rm, self._stream())
         return self.codes, self.meta
 
     @property
@@ -341,12 +343,9 @@ class VecGridworldCtf:
     def step_observe(self, actions, auto_reset=False, want_f64=False, reverse_mask=None):
         """step() then observe() in one call -> (rewards, done, obs, meta)."""
         a = self._check_dev(actions, _torch().int8, self.n_envs * self.N_AGENTS)
-        rm = _abi.REVERSE_DEFAULT if reverse_mask is None else int(reverse_mask) & ((1 << self.N_AGENTS) - 1)
-        _abi.check(self._lib.ctf_step_observe(self._h, a, C.c_void_p(self.rewards.data_ptr()),
-                                              C.c_void_p(self.rewards64.data_ptr()) if want_f64 else None,
-                                              C.c_void_p(self.done.data_ptr()), C.c_void_p(self.obs.data_ptr()),
-                                              C.c_void_p(self.meta.data_ptr()), rm,
-                                              _abi.STEP_AUTO_RESET if auto_reset else 0, self._stream()), self._lib)
+        self._call("ctf_step_observe", a, _abi.ptr(self.rewards), _abi.ptr(self.rewards64 if want_f64 else None), _abi.ptr(self.done),
+                   _abi.ptr(self.obs), _abi.ptr(self.meta), self._reverse_bits(reverse_mask), _abi.STEP_AUTO_RESET if auto_reset else 0,
+                   self._stream())
         return self.rewards, self.done, self.obs, self.meta
 
     def host_step(self, actions=None, py_in=None, np_in=None, reverse_mask=None, rng_out=False, view=None, obs=None, meta=None):
@@ -354,22 +353,20 @@ class VecGridworldCtf:
         or None (no step); py_in / np_in: uint32 numpy [625] to install before the step; -> (rewards float64 [N], done, status
         bits, view, py_out, np_out) with obs (uint8 [N, C, G, G]) and meta (float16 [N, M]) filled in place when given."""
         n = self.N_AGENTS
-        rm = _abi.REVERSE_DEFAULT if reverse_mask is None else int(reverse_mask) & ((1 << n) - 1)
         ptr = lambda a: None if a is None else a.__array_interface__["data"][0]  # (the plain address: a third of the cost of ctypes.data_as)
         rewards = np.zeros(n, np.float64)
         done, status = C.c_int32(0), C.c_uint32(0)
         view = view if view is not None else _abi.CtfStateView()
         py_out = np.empty(625, np.uint32) if rng_out else None
         np_out = np.empty(625, np.uint32) if rng_out else None
-        _abi.check(self._lib.ctf_host_step(self._h, ptr(actions), ptr(py_in), ptr(np_in), rm, 0, ptr(rewards), C.byref(done),
-                                           C.byref(status), C.byref(view), ptr(py_out), ptr(np_out), ptr(obs), ptr(meta),
-                                           self._stream()), self._lib)
+        self._call("ctf_host_step", ptr(actions), ptr(py_in), ptr(np_in), self._reverse_bits(reverse_mask), 0, ptr(rewards), C.byref(done),
+                   C.byref(status), C.byref(view), ptr(py_out), ptr(np_out), ptr(obs), ptr(meta), self._stream())
         return rewards, bool(done.value), status.value, view, py_out, np_out
 
     def random_actions(self, out, seed, step, env_offset=0):
         """Fill ``out`` (int8 [E, N]) with the synthetic Philox action stream of bench.py / the tests."""
         a = self._check_dev(out, _torch().int8, self.n_envs * self.N_AGENTS)
-        _abi.check(self._lib.ctf_random_actions(self._h, a, int(seed), int(step), int(env_offset), self._stream()), self._lib)
+        self._call("ctf_random_actions", a, int(seed), int(step), int(env_offset), self._stream())
         return out
 
     def counters(self):
@@ -380,14 +377,13 @@ class VecGridworldCtf:
         met = torch.empty((E, _abi.N_METRICS, N), dtype=torch.int32, device=self.device)
         caps = torch.empty((E, 2), dtype=torch.int32, device=self.device)
         steps = torch.empty((E,), dtype=torch.int32, device=self.device)
-        _abi.check(self._lib.ctf_export_counters(self._h, C.c_void_p(met.data_ptr()), C.c_void_p(caps.data_ptr()),
-                                                 C.c_void_p(steps.data_ptr()), self._stream()), self._lib)
+        self._call("ctf_export_counters", _abi.ptr(met), _abi.ptr(caps), _abi.ptr(steps), self._stream())
         return met, caps, steps
 
     def action_mask(self):
         """uint8 [N, 9]: 1 where the action is legal for the agent's type (agent_network.py:66-75)."""
         m = np.zeros((self.N_AGENTS, _abi.N_ACTIONS), np.uint8)
-        _abi.check(self._lib.ctf_action_mask(self._h, m.ctypes.data_as(C.c_void_p)), self._lib)
+        self._call("ctf_action_mask", m.ctypes.data_as(C.c_void_p))
         return m
 
     # -- snapshots: whole env states as opaque device records (include/ctf_env.h, ctf_save_states) ---------------------------
@@ -436,7 +432,7 @@ class VecGridworldCtf:
             raise ValueError(f"{what}: expected shape [{'n' if n is None else n}, {S}], got {list(buf.shape)}")
         if not buf.is_contiguous() or buf.data_ptr() % 16:
             raise ValueError(f"{what}: the record buffer must be contiguous and 16-byte aligned")
-        return C.c_void_p(buf.data_ptr())
+        return _abi.ptr(buf)
 
     def save_states(self, idx=None, out=None):
         """Records of envs ``idx`` (None: all) -> uint8 [n, snapshot_bytes] on the env's device (``out`` if given).  Stream-ordered:
@@ -446,8 +442,7 @@ class VecGridworldCtf:
         if out is None:
             out = torch.empty((n, self.snapshot_bytes), dtype=torch.uint8, device=self.device)
         ptr = self._records(out, n, "save_states")
-        _abi.check(self._lib.ctf_save_states(self._h, None if ix is None else C.c_void_p(ix.data_ptr()), n, ptr, self._stream()),
-                   self._lib)
+        self._call("ctf_save_states", _abi.ptr(ix), n, ptr, self._stream())
         return out
 
     def load_states(self, buf, idx=None, check=True):
@@ -466,8 +461,7 @@ class VecGridworldCtf:
             raise ValueError(f"load_states: {n} records but {m} indices")
         if check and ix is not None and torch.unique(ix).numel() != n:
             raise ValueError("load_states: repeated indices")
-        _abi.check(self._lib.ctf_load_states(self._h, ptr, None if ix is None else C.c_void_p(ix.data_ptr()), n, self._stream()),
-                   self._lib)
+        self._call("ctf_load_states", ptr, _abi.ptr(ix), n, self._stream())
 
     def clone_envs(self, src_idx, dst_idx, check=True):
         """Env ``dst_idx[k]`` := the state of env ``src_idx[k]`` (through a scratch buffer this object owns, so the two sets may
@@ -499,22 +493,21 @@ class VecGridworldCtf:
             raise ValueError(f"harvest: expected a contiguous table of shape [n_groups >= 1, {H}], got {list(acc.shape)}")
         g = None if groups is None else self._check_dev(groups, torch.int32, self.n_envs)
         m = None if mask is None else self._check_dev(mask, torch.uint8, self.n_envs)
-        _abi.check(self._lib.ctf_harvest_episodes(self._h, g, int(acc.shape[0]), m, _abi.HARVEST_ALL if all_envs else 0,
-                                                  C.c_void_p(acc.data_ptr()), self._stream()), self._lib)
+        self._call("ctf_harvest_episodes", g, int(acc.shape[0]), m, _abi.HARVEST_ALL if all_envs else 0, _abi.ptr(acc), self._stream())
         return acc
 
     # -- host views ---------------------------------------------------------------------------
     def get_state(self, env_index):
         v = _abi.CtfStateView()
-        _abi.check(self._lib.ctf_get_state(self._h, int(env_index), C.byref(v)), self._lib)
+        self._call("ctf_get_state", int(env_index), C.byref(v))
         return v
 
     def set_state(self, env_index, view):
-        _abi.check(self._lib.ctf_set_state(self._h, int(env_index), C.byref(view)), self._lib)
+        self._call("ctf_set_state", int(env_index), C.byref(view))
 
     def status(self):
         bits = C.c_uint32(0)
-        _abi.check(self._lib.ctf_status(self._h, C.byref(bits), self._stream()), self._lib)
+        self._call("ctf_status", C.byref(bits), self._stream())
         return bits.value
 
 

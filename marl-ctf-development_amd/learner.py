@@ -342,8 +342,7 @@ class PPOLearner:
             except ImportError:  # pragma: no cover
                 import _abi
             lib = _abi.load_library()
-            if lib.ctf_policy_set_deterministic(dev.index, self._det_ws.data_ptr(), self._det_ws.numel()) != 0:
-                raise _abi.CtfLibraryError("ctf_policy_set_deterministic: " + (lib.ctf_policy_last_error() or b"").decode())
+            _abi.call(lib, "ctf_policy_set_deterministic", dev.index, _abi.ptr(self._det_ws), self._det_ws.numel())
         try:
             yield
         finally:

@@ -18,7 +18,9 @@ Numerics: bf16 operands, float32 accumulation; against the float32 reference net
 1e-2 (tests/test_gpu_policy_native.py states the tolerance).  The kernel-side copies of the weights are rebuilt by
 ``prepare()``; it runs by itself on first use and whenever a parameter was updated in place or moved since.
 """
+import copy
 import ctypes as C
+import hashlib
 import math
 import os
 
@@ -169,6 +171,54 @@ def fc1_patch_map(grid_size, meta_len):
     return np.rint(np.asarray(fc1_patch_fragments(stand_in, grid_size, meta_len), np.float64) / _TWO_LOG2E).astype(np.int64) - 1
 
 
+# -- input checks of the entry points that take the compact observation (the texts are the callers' contract) ------------------
+def _check_codes(codes, grid_size, lead):
+    """``lead``: the names of the leading axes, "E, N" (env, agent) or "B" (one sample per row of a training batch)."""
+    n_lead = lead.count(",") + 1
+    if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape[n_lead:]) == (grid_size,) * 2):
+        raise ValueError(f"codes must be a contiguous uint8 CUDA tensor [{lead}, G, G]")
+
+
+def _check_meta(meta, shape, lead):
+    if not (meta.is_cuda and meta.dtype == torch.float16 and meta.is_contiguous() and tuple(meta.shape) == tuple(shape)):
+        raise ValueError(f"meta must be a contiguous float16 CUDA tensor [{lead}, M]")
+
+
+def _check_self_cells(self_cells, E, N):
+    if not (self_cells is not None and self_cells.is_cuda and self_cells.dtype == torch.int16 and self_cells.is_contiguous()
+            and tuple(self_cells.shape) == (E, N)):
+        raise ValueError("self_cells must be a contiguous int16 CUDA tensor [E, N]")
+
+
+def _agent_list(agent_idx):
+    """agent_idx (list, tuple, numpy array or tensor) -> (list of ints, the same as the ABI's int32 array)."""
+    sel = [int(i) for i in (agent_idx.tolist() if hasattr(agent_idx, "tolist") else agent_idx)]
+    return sel, (C.c_int32 * len(sel))(*sel)
+
+
+def _search_placement(make, time, tries, slow_over_fast):
+    """Large allocations on this pool come in two kinds, the kind independent from one allocation to the next even
+    after a free (tools/placement_probe2.py): ``make()`` candidates are timed by ``time(candidate)`` — the real work — until both kinds
+    were seen (the slowest at ``slow_over_fast`` x the fastest) or ``tries`` candidates, or an allocation fails.  -> (the fastest, the
+    earlier one on a tie; every candidate's time).  Two candidates are held at most, and only here — ``make`` hands its buffers
+    over: the loser goes back to the DRIVER at once, so that the next candidate is a fresh allocation and not that block again.
+    (empty_cache returns the allocator's FREE blocks only — no live tensor of a co-resident learner is touched; it re-allocates what
+    it had cached.)"""
+    best = make()
+    times = [time(best)]
+    while len(times) < tries and max(times) < slow_over_fast * min(times):
+        try:
+            cand = make()
+        except torch.cuda.OutOfMemoryError:
+            break
+        times.append(time(cand))
+        if times[-1] < min(times[:-1]):
+            best, cand = cand, best
+        del cand
+        torch.cuda.empty_cache()
+    return best, times
+
+
 class _NativeFront(torch.autograd.Function):
     """conv1 -> tanh -> conv2 -> tanh -> flatten ++ metadata of a training step with native kernels for everything but the two
     weight gradients: the FORWARD is ctf_policy_features_train (the activation row fc1 consumes, plus the one-hot image and
@@ -193,8 +243,7 @@ class _NativeFront(torch.autograd.Function):
         b, dev = act.shape[0], act.device
         bf, cl = torch.bfloat16, torch.channels_last
         conv_bwd = torch.ops.aten.convolution_backward
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ptr, stream = _abi.ptr, _abi.stream_ptr(dev)
         d_act = d_act.to(bf).contiguous()
         if ctx.native_wgrad and ctx.fused:
             # round 4: conv2's data AND weight gradient in one pass (dz2 never leaves the CU), then conv1's weight gradient from the dz1
@@ -202,9 +251,8 @@ class _NativeFront(torch.autograd.Function):
             dz1 = torch.empty((b, g1, g1, 16), dtype=bf, device=dev)
             grads = torch.zeros(48 + 32 * 16 * 9 + 16 * 16 * 9, dtype=torch.float32, device=dev)
             db2, db1, dw2, dw1 = grads[:32], grads[32:48], grads[48:48 + 32 * 16 * 9], grads[48 + 32 * 16 * 9:]
-            if lib.ctf_policy_front_backward(ptr(d_act), ptr(act), ptr(h1), ptr(h0), ptr(ctx.f2t), b, g, m, ptr(dz1), ptr(dw2), ptr(dw1), ptr(db2),
-                                             ptr(db1), dev.index, stream) != 0:
-                raise _abi.CtfLibraryError("ctf_policy_front_backward: " + (lib.ctf_policy_last_error() or b"").decode())
+            _abi.call(lib, "ctf_policy_front_backward", ptr(d_act), ptr(act), ptr(h1), ptr(h0), ptr(ctx.f2t), b, g, m, ptr(dz1), ptr(dw2), ptr(dw1),
+                      ptr(db2), ptr(db1), dev.index, stream)
             return None, None, None, dw1.view(16, 16, 3, 3)[:, :c_in].contiguous(), db1, dw2.view(32, 16, 3, 3), db2
         # one launch: tanh' of conv2's output (rows of the activation matrix in, channels-last out), conv2's data gradient, tanh' of
         # conv1's output, both bias gradients in float32; the library is left with the two weight gradients
@@ -212,13 +260,11 @@ class _NativeFront(torch.autograd.Function):
         dz1 = torch.empty((b, g1, g1, 16), dtype=bf, device=dev)
         db = torch.zeros(48, dtype=torch.float32, device=dev)
         db2, db1 = db[:32], db[32:]
-        if lib.ctf_policy_front_dgrad(ptr(d_act), ptr(act), ptr(h1), ptr(ctx.f2t), b, g, m, ptr(dz2), ptr(dz1), ptr(db2), ptr(db1), dev.index, stream) != 0:
-            raise _abi.CtfLibraryError("ctf_policy_front_dgrad: " + (lib.ctf_policy_last_error() or b"").decode())
+        _abi.call(lib, "ctf_policy_front_dgrad", ptr(d_act), ptr(act), ptr(h1), ptr(ctx.f2t), b, g, m, ptr(dz2), ptr(dz1), ptr(db2), ptr(db1), dev.index, stream)
         if ctx.native_wgrad:  # both weight gradients on the matrix cores too (h0 here is the codes: the kernel builds the one-hot image itself)
             dw = torch.zeros(32 * 16 * 9 + 16 * 16 * 9, dtype=torch.float32, device=dev)
             dw2, dw1 = dw[:32 * 16 * 9], dw[32 * 16 * 9:]
-            if lib.ctf_policy_front_wgrad(ptr(dz2), ptr(h1), ptr(dz1), ptr(h0), b, g, ptr(dw2), ptr(dw1), dev.index, stream) != 0:
-                raise _abi.CtfLibraryError("ctf_policy_front_wgrad: " + (lib.ctf_policy_last_error() or b"").decode())
+            _abi.call(lib, "ctf_policy_front_wgrad", ptr(dz2), ptr(h1), ptr(dz1), ptr(h0), b, g, ptr(dw2), ptr(dw1), dev.index, stream)
             return None, None, None, dw1.view(16, 16, 3, 3)[:, :c_in].contiguous(), db1, dw2.view(32, 16, 3, 3), db2
         dz2, dz1 = dz2.permute(0, 3, 1, 2), dz1.permute(0, 3, 1, 2)
         h1i = h1.view(b, g1, g1, 16).permute(0, 3, 1, 2)
@@ -251,10 +297,8 @@ class _TailLinear(torch.autograd.Function):
         n_out, n_in = wb.shape
         grads = torch.zeros(n_out * n_in + n_out, dtype=torch.float32, device=dev)
         dw, db = grads[:n_out * n_in], (grads[n_out * n_in:] if ctx.has_bias else None)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        if ctx.lib.ctf_policy_linear_wgrad(ptr(dy), ptr(x), dy.shape[0], n_out, n_in, ptr(dw), ptr(db), dev.index,
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) != 0:
-            raise _abi.CtfLibraryError("ctf_policy_linear_wgrad: " + (ctx.lib.ctf_policy_last_error() or b"").decode())
+        ptr = _abi.ptr
+        _abi.call(ctx.lib, "ctf_policy_linear_wgrad", ptr(dy), ptr(x), dy.shape[0], n_out, n_in, ptr(dw), ptr(db), dev.index, _abi.stream_ptr(dev))
         dx = torch.mm(dy, wb) if ctx.needs_input_grad[0] else None
         return dx, dw.view(n_out, n_in), db, None
 
@@ -295,10 +339,7 @@ class _Fc1Linear(torch.autograd.Function):
             if m % 32 == 0 and kp % 64 == 0:
                 dx = torch.empty((m, kp), dtype=torch.bfloat16, device=dev)
                 wt = wb.t().contiguous()
-                ptr = lambda t: C.c_void_p(t.data_ptr())
-                if ctx.lib.ctf_policy_fc1_dgrad(ptr(dy), ptr(wt), m, kp, ptr(dx), dev.index,
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)) != 0:
-                    raise _abi.CtfLibraryError("ctf_policy_fc1_dgrad: " + (ctx.lib.ctf_policy_last_error() or b"").decode())
+                _abi.call(ctx.lib, "ctf_policy_fc1_dgrad", _abi.ptr(dy), _abi.ptr(wt), m, kp, _abi.ptr(dx), dev.index, _abi.stream_ptr(dev))
             else:
                 dx = torch.mm(dy, wb)
         return dx, dw, None
@@ -341,8 +382,6 @@ class CtfPolicyNative(CtfPolicy):
         """A new module: a key that depends on where torch's CPU generator stands (read, not advanced) — building a module moves
         it (weight init), so every module built gets its own, and the same torch.manual_seed gives the same keys.  A copy:
         derived from its parent's key and the number of copies the parent has handed out."""
-        import hashlib
-
         if parent is None:
             material = torch.get_rng_state().numpy().tobytes()
         else:
@@ -361,8 +400,6 @@ class CtfPolicyNative(CtfPolicy):
         return d
 
     def __deepcopy__(self, memo):  # a COPY samples from its own stream (see __init__); a restored pickle keeps the original's
-        import copy
-
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         new.__setstate__(copy.deepcopy(self.__getstate__(), memo))
@@ -371,8 +408,6 @@ class CtfPolicyNative(CtfPolicy):
 
     def clone(self, reseed=True):
         """A deep copy; ``reseed=False`` keeps the action sampler's (key, offset), e.g. to replay the original's draws."""
-        import copy
-
         new = copy.deepcopy(self)
         if not reseed:
             new._seed, new._calls = self._seed, self._calls
@@ -450,30 +485,23 @@ class CtfPolicyNative(CtfPolicy):
         each row's bit 7 sits); derived from ``codes`` when not given."""
         p = self._ready()
         E, N = int(codes.shape[0]), int(codes.shape[1])
-        if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape[2:]) == (self.grid_size,) * 2):
-            raise ValueError("codes must be a contiguous uint8 CUDA tensor [E, N, G, G]")
-        if not (meta.is_cuda and meta.dtype == torch.float16 and meta.is_contiguous() and tuple(meta.shape) == (E, N, self.metadata_size)):
-            raise ValueError("meta must be a contiguous float16 CUDA tensor [E, N, M]")
-        sel = [int(i) for i in (agent_idx.tolist() if hasattr(agent_idx, "tolist") else agent_idx)]
+        _check_codes(codes, self.grid_size, "E, N")
+        _check_meta(meta, (E, N, self.metadata_size), "E, N")
+        sel, sel_arr = _agent_list(agent_idx)
         if out is None:
             out = torch.empty((len(sel) * E, p["kp"]), dtype=torch.bfloat16, device=codes.device)
         elif not (out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (len(sel) * E, p["kp"])):
             raise ValueError("out must be a contiguous bfloat16 tensor [len(agent_idx) * E, Kp]")
-        sel_arr = (C.c_int32 * len(sel))(*sel)
-        sc_ptr = None
         if shared_view and len(sel) <= 4:
             if self_cells is None:
                 self_cells = (codes >> 7).flatten(2).argmax(dim=2).to(torch.int16)
-            if not (self_cells.is_cuda and self_cells.dtype == torch.int16 and self_cells.is_contiguous() and tuple(self_cells.shape) == (E, N)):
-                raise ValueError("self_cells must be a contiguous int16 CUDA tensor [E, N]")
-            sc_ptr = C.c_void_p(self_cells.data_ptr())
-        rc = p["lib"].ctf_policy_features(
-            C.c_void_p(codes.data_ptr()), C.c_void_p(meta.data_ptr()), E, N, self.grid_size, self.metadata_size, sel_arr, len(sel),
-            C.c_void_p(p["f1"].data_ptr()), C.c_void_p(p["b1"].data_ptr()), C.c_void_p(p["f2"].data_ptr()),
-            C.c_void_p(p["b2"].data_ptr()), C.c_void_p(out.data_ptr()), sc_ptr, codes.device.index,
-            C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream))
-        if rc != 0:
-            raise _abi.CtfLibraryError("ctf_policy_features: " + (p["lib"].ctf_policy_last_error() or b"").decode())
+            _check_self_cells(self_cells, E, N)
+        else:
+            self_cells = None  # (the kernel then finds each row's bit 7 itself)
+        ptr = _abi.ptr
+        _abi.call(p["lib"], "ctf_policy_features", ptr(codes), ptr(meta), E, N, self.grid_size, self.metadata_size, sel_arr, len(sel),
+                  ptr(p["f1"]), ptr(p["b1"]), ptr(p["f2"]), ptr(p["b2"]), ptr(out), ptr(self_cells), codes.device.index,
+                  _abi.stream_ptr(codes.device))
         return out
 
     # -- fc1 carried through the shared view (include/ctf_policy.h, "fc1 without the per-agent activation matrix") ------------------
@@ -511,34 +539,24 @@ class CtfPolicyNative(CtfPolicy):
         p = self._ready()
         lib = p["lib"]
         E, N = int(codes.shape[0]), int(codes.shape[1])
-        sel = [int(i) for i in (agent_idx.tolist() if hasattr(agent_idx, "tolist") else agent_idx)]
+        sel, sel_arr = _agent_list(agent_idx)
         A, dev = len(sel), codes.device
-        if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape[2:]) == (self.grid_size,) * 2):
-            raise ValueError("codes must be a contiguous uint8 CUDA tensor [E, N, G, G]")
-        if not (meta.is_cuda and meta.dtype == torch.float16 and meta.is_contiguous() and tuple(meta.shape) == (E, N, self.metadata_size)):
-            raise ValueError("meta must be a contiguous float16 CUDA tensor [E, N, M]")
-        if not (self_cells is not None and self_cells.is_cuda and self_cells.dtype == torch.int16 and self_cells.is_contiguous() and tuple(self_cells.shape) == (E, N)):
-            raise ValueError("self_cells must be a contiguous int16 CUDA tensor [E, N]")
+        _check_codes(codes, self.grid_size, "E, N")
+        _check_meta(meta, (E, N, self.metadata_size), "E, N")
+        _check_self_cells(self_cells, E, N)
         if not (1 <= A <= 4 and self.fact_supported()):
             raise ValueError("the factored fc1 path takes 1..4 agents of one view, grid_size 11 or 15, metadata_size <= 32")
         b = self._fact_buffers(E, A, dev)
-        sel_arr = (C.c_int32 * A)(*sel)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ptr, stream = _abi.ptr, _abi.stream_ptr(dev)
         G, M = self.grid_size, self.metadata_size
-
-        def ok(rc, what):
-            if rc != 0:
-                raise _abi.CtfLibraryError(what + ": " + (lib.ctf_policy_last_error() or b"").decode())
-
-        ok(lib.ctf_policy_fact_bucket(ptr(self_cells), E, N, G, sel_arr, A, ptr(b["work"]), ptr(b["slot_of"]), ptr(b["row_of_slot"]),
-                                      dev.index, stream), "ctf_policy_fact_bucket")
+        _abi.call(lib, "ctf_policy_fact_bucket", ptr(self_cells), E, N, G, sel_arr, A, ptr(b["work"]), ptr(b["slot_of"]), ptr(b["row_of_slot"]),
+                  dev.index, stream)
 
         def front_and_gemm(view):
-            ok(lib.ctf_policy_features_fact(ptr(codes), ptr(meta), ptr(self_cells), E, N, G, M, sel_arr, A, ptr(p["f1"]), ptr(p["b1"]), ptr(p["f2"]),
-                                            ptr(p["b2"]), ptr(b["slot_of"]), ptr(view), ptr(b["prow"]), dev.index, stream), "ctf_policy_features_fact")
+            _abi.call(lib, "ctf_policy_features_fact", ptr(codes), ptr(meta), ptr(self_cells), E, N, G, M, sel_arr, A, ptr(p["f1"]), ptr(p["b1"]),
+                      ptr(p["f2"]), ptr(p["b2"]), ptr(b["slot_of"]), ptr(view), ptr(b["prow"]), dev.index, stream)
             if self.native_view_gemm or not MM_OUT_DTYPE:  # float32 out either way: the patch product is added before the one rounding
-                ok(lib.ctf_policy_view_gemm(ptr(view), ptr(p["fc1_view_w"]), E, b["kv"], ptr(b["yview"]), dev.index, stream), "ctf_policy_view_gemm")
+                _abi.call(lib, "ctf_policy_view_gemm", ptr(view), ptr(p["fc1_view_w"]), E, b["kv"], ptr(b["yview"]), dev.index, stream)
             elif E % 4 == 0:
                 # the library's fastest form of this product (tools/view_gemm_forms_probe.py, 65 536 x 4 096: 0.154 ms; the plain
                 # mm(view, W^T stored [KV, 256]) 0.185, mm against the k-contiguous W 0.170): four row ranges as a batch, W k-contiguous
@@ -548,13 +566,10 @@ class CtfPolicyNative(CtfPolicy):
                 torch.mm(view, p["fc1_view_w"].t(), out_dtype=torch.float32, out=b["yview"])
 
         if not b.get("placed"):
-            # Large allocations on this pool come in two kinds: the slow one costs the front's stores and the GEMM's reads
-            # of the view matrix ~25 % (0.22 against 0.16 ms for the GEMM of a 65 536-env step).  Once per buffer: candidates are timed
-            # with the real work, a loser goes back to the driver at once (two held at most), until both kinds were seen or 8 tries.
+            # The slow kind of allocation (_search_placement) costs the front's stores and the GEMM's reads of the view matrix ~25 % (0.22
+            # against 0.16 ms for the GEMM of a 65 536-env step).  Once per buffer.  (tune_placement = False keeps the search out of a
+            # timed collect(); several ranks on ONE device — CTF_BENCH_ONE_DEVICE, a rehearsal — would time each other: no search there)
             b["placed"] = True
-            import os
-
-            # (several ranks on ONE device — CTF_BENCH_ONE_DEVICE, a rehearsal — would time each other: no search there)
             if b["view"].numel() * 2 > (256 << 20) and self.tune_placement and not os.environ.get("CTF_BENCH_ONE_DEVICE"):
                 def probe(view):
                     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -565,44 +580,16 @@ class CtfPolicyNative(CtfPolicy):
                     t1.record()
                     t1.synchronize()
                     return t0.elapsed_time(t1) / 2
-                times = [probe(b["view"])]
-                while len(times) < 8 and max(times) < 1.08 * min(times):
-                    try:
-                        cand = torch.empty_like(b["view"])
-                    except torch.cuda.OutOfMemoryError:
-                        break
-                    times.append(probe(cand))
-                    if times[-1] < min(times[:-1]):
-                        b["view"], cand = cand, b["view"]
-                    # the loser goes back to the DRIVER: the next candidate must be a fresh allocation, not this block again.  (empty_cache
-                    # returns the allocator's FREE blocks only — no live tensor of a co-resident learner is touched; it re-allocates what it
-                    # had cached.  tune_placement = False, or prepare_placement() from a warm-up, keeps this out of a timed collect().)
-                    del cand
-                    torch.cuda.empty_cache()
-                self.placement_probe_ms = times
+
+                def candidate():  # the first one is the buffer _fact_buffers allocated: handed over, the search is its only holder
+                    return b.pop("view") if "view" in b else torch.empty((E, b["kv"]), dtype=torch.bfloat16, device=dev)
+
+                b["view"], self.placement_probe_ms = _search_placement(candidate, probe, tries=8, slow_over_fast=1.08)
         front_and_gemm(b["view"])
+        patch = (ptr(b["prow"]), ptr(b["row_of_slot"]), ptr(b["work"]), ptr(b["yview"]), ptr(p["pf"]), ptr(p["fc1_b32"]), E, A, G, M)
         if head is not None:
-            B = A * E
-            f32 = dict(dtype=torch.float32, device=dev)
-            action = torch.empty(B, dtype=torch.int32, device=dev)
-            logprob, entropy, value = torch.empty(B, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
-            logits = torch.empty((B, self.n_actions), **f32) if head.get("want_logits") else None
-            mask, given = head.get("mask"), head.get("given")
-            if mask is not None:
-                mask = mask.reshape(-1).to(torch.float32).contiguous()
-                if mask.numel() != B:
-                    raise ValueError("masking_decision_tensor must have one entry per sample")
-            if given is not None:
-                given = given.reshape(-1).to(torch.int32).contiguous()
-            self._calls += 1
-            optr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            ok(lib.ctf_policy_fc1_patch_head(ptr(b["prow"]), ptr(b["row_of_slot"]), ptr(b["work"]), ptr(b["yview"]), ptr(p["pf"]), ptr(p["fc1_b32"]),
-                                             E, A, G, M, ptr(p["t2"]), ptr(p["tb2"]), ptr(p["th"]), ptr(p["tbh"]), optr(mask), optr(given),
-                                             self.n_actions, C.c_uint64(self._seed), C.c_uint64(self._calls), ptr(action), ptr(logprob),
-                                             ptr(entropy), ptr(value), optr(logits), dev.index, stream), "ctf_policy_fc1_patch_head")
-            return action, logprob, entropy, value, logits
-        ok(lib.ctf_policy_fc1_patch(ptr(b["prow"]), ptr(b["row_of_slot"]), ptr(b["work"]), ptr(b["yview"]), ptr(p["pf"]), ptr(p["fc1_b32"]),
-                                    E, A, G, M, ptr(b["y1"]), dev.index, stream), "ctf_policy_fc1_patch")
+            return self._head_call(p, A * E, dev, head.get("mask"), head.get("given"), head.get("want_logits"), "ctf_policy_fc1_patch_head", *patch)
+        _abi.call(lib, "ctf_policy_fc1_patch", *patch, ptr(b["y1"]), dev.index, stream)
         return b["y1"]
 
     # -- the forward of a training step ----------------------------------------------------------------
@@ -611,18 +598,13 @@ class CtfPolicyNative(CtfPolicy):
         input image bf16 [B, G*G, 16], tanh(conv1) bf16 [B, (G-2)^2, 16]) — ctf_policy_features_train."""
         p = self._ready()
         b, g = int(codes.shape[0]), self.grid_size
-        if not (codes.is_cuda and codes.dtype == torch.uint8 and codes.is_contiguous() and tuple(codes.shape[1:]) == (g, g)):
-            raise ValueError("codes must be a contiguous uint8 CUDA tensor [B, G, G]")
-        if not (meta.is_cuda and meta.dtype == torch.float16 and meta.is_contiguous() and tuple(meta.shape) == (b, self.metadata_size)):
-            raise ValueError("meta must be a contiguous float16 CUDA tensor [B, M]")
+        _check_codes(codes, g, "B")
+        _check_meta(meta, (b, self.metadata_size), "B")
         new = lambda *shape: torch.empty(shape, dtype=torch.bfloat16, device=codes.device)
         act, h0, h1 = new(b, p["kp"]), (new(b, g * g, 16) if want_h0 else None), new(b, (g - 2) ** 2, 16)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = p["lib"].ctf_policy_features_train(ptr(codes), ptr(meta), b, g, self.metadata_size, ptr(p["f1"]), ptr(p["b1"]), ptr(p["f2"]),
-                                                ptr(p["b2"]), ptr(act), ptr(h0), ptr(h1), codes.device.index,
-                                                C.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream))
-        if rc != 0:
-            raise _abi.CtfLibraryError("ctf_policy_features_train: " + (p["lib"].ctf_policy_last_error() or b"").decode())
+        ptr = _abi.ptr
+        _abi.call(p["lib"], "ctf_policy_features_train", ptr(codes), ptr(meta), b, g, self.metadata_size, ptr(p["f1"]), ptr(p["b1"]), ptr(p["f2"]),
+                  ptr(p["b2"]), ptr(act), ptr(h0), ptr(h1), codes.device.index, _abi.stream_ptr(codes.device))
         return act, h0, h1
 
     def trunk_codes(self, codes, metadata):
@@ -657,11 +639,9 @@ class CtfPolicyNative(CtfPolicy):
         return value.float(), logits.float()
 
     def _features_tuned(self, codes, meta, agent_idx, shared_view, self_cells, tries=12, slow_over_fast=1.1):
-        """features_from_codes into a persistent activation buffer.  Large allocations on this pool come in two kinds — the slow one
-        costs both the kernel's stores and the GEMM's reads ~20 % — and the kind is independent from one allocation to
-        the next even after a free (tools/placement_probe2.py): on first use candidates are timed with the real work (front kernel + fc1
-        GEMM), a loser goes back to the driver at once (two buffers held at most), and the search stops as soon as it has seen both
-        kinds, keeping the fast one."""
+        """features_from_codes into a persistent activation buffer.  The slow kind of allocation (_search_placement) costs both the
+        kernel's stores and the GEMM's reads ~20 %: on first use candidates are timed with the real work (front kernel +
+        fc1 GEMM) and the fast one is kept.  (Unlike the factored path's view buffer, searched whatever ``tune_placement`` says.)"""
         p = self._ready()
         rows = len(agent_idx) * int(codes.shape[0])
         key = (rows, p["kp"], codes.device.index)
@@ -681,18 +661,10 @@ class CtfPolicyNative(CtfPolicy):
             return a.elapsed_time(b) / 2
 
         new = lambda: torch.empty((rows, p["kp"]), dtype=torch.bfloat16, device=codes.device)
-        buf = new()
-        times = [probe(buf)] if rows * p["kp"] * 2 > (256 << 20) else [0.0]
-        while 0.0 < min(times) and len(times) < tries and max(times) < slow_over_fast * min(times):  # until both kinds were seen
-            try:
-                cand = new()
-            except torch.cuda.OutOfMemoryError:
-                break
-            times.append(probe(cand))
-            if times[-1] < min(times[:-1]):
-                buf = cand
-            del cand
-            torch.cuda.empty_cache()
+        if rows * p["kp"] * 2 > (256 << 20):
+            buf, times = _search_placement(new, probe, tries, slow_over_fast)
+        else:
+            buf, times = new(), [0.0]
         self._act_bufs[key] = buf
         self.placement_probe_ms = times
         return self.features_from_codes(codes, meta, agent_idx, out=buf, shared_view=shared_view, self_cells=self_cells)
@@ -705,12 +677,16 @@ class CtfPolicyNative(CtfPolicy):
 
     def _head(self, y1, mask=None, given=None, want_logits=False):
         """ctf_policy_head on fc1's scaled pre-activation y1 (bf16 [B, 256])."""
-        p = self._ready()
-        B, dev = y1.shape[0], y1.device
-        f32 = dict(dtype=torch.float32, device=dev)
+        return self._head_call(self._ready(), y1.shape[0], y1.device, mask, given, want_logits, "ctf_policy_head", _abi.ptr(y1), y1.shape[0])
+
+    def _head_call(self, p, B, dev, mask, given, want_logits, name, *lead):
+        """The host side of the network's tail for B samples: the outputs, ``mask`` / ``given`` in the kernel's form, the sampler's next
+        offset, and the launch — entry point ``name``, whose arguments are ``lead`` followed by what both entry points share
+        (include/ctf_policy.h: ctf_policy_head, ctf_policy_fc1_patch_head)."""
+        out = dict(dtype=torch.float32, device=dev)
         action = torch.empty(B, dtype=torch.int32, device=dev)
-        logprob, entropy, value = torch.empty(B, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
-        logits = torch.empty((B, self.n_actions), **f32) if want_logits else None
+        logprob, entropy, value = torch.empty(B, **out), torch.empty(B, **out), torch.empty(B, **out)
+        logits = torch.empty((B, self.n_actions), **out) if want_logits else None
         if mask is not None:
             mask = mask.reshape(-1).to(torch.float32).contiguous()
             if mask.numel() != B:
@@ -718,13 +694,10 @@ class CtfPolicyNative(CtfPolicy):
         if given is not None:
             given = given.reshape(-1).to(torch.int32).contiguous()
         self._calls += 1
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = p["lib"].ctf_policy_head(
-            ptr(y1), B, ptr(p["t2"]), ptr(p["tb2"]), ptr(p["th"]), ptr(p["tbh"]), ptr(mask), ptr(given), self.n_actions,
-            C.c_uint64(self._seed), C.c_uint64(self._calls), ptr(action), ptr(logprob), ptr(entropy), ptr(value), ptr(logits),
-            dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise _abi.CtfLibraryError("ctf_policy_head: " + (p["lib"].ctf_policy_last_error() or b"").decode())
+        ptr = _abi.ptr
+        _abi.call(p["lib"], name, *lead, ptr(p["t2"]), ptr(p["tb2"]), ptr(p["th"]), ptr(p["tbh"]), ptr(mask), ptr(given), self.n_actions,
+                  C.c_uint64(self._seed), C.c_uint64(self._calls), ptr(action), ptr(logprob), ptr(entropy), ptr(value), ptr(logits),
+                  dev.index, _abi.stream_ptr(dev))
         return action, logprob, entropy, value, logits
 
     def trunk_from_codes(self, codes, meta, agent_idx):

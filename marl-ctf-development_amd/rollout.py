@@ -197,15 +197,12 @@ class BatchedRolloutCollector:
         f32 = lambda x: x.reshape(-1).to(torch.float32).contiguous()
         a_act, o_act, a_lp, a_val = i32(a_act), i32(o_act), f32(a_lp), f32(a_val)
         sl = slice(t * A, (t + 1) * A)
-        ptr = lambda x: C.c_void_p(x.data_ptr())
+        ptr = _abi.ptr
         g = vec.GRID_SIZE
-        rc = sa["lib"].ctf_rollout_store_step(
-            ptr(codes), ptr(meta), E, N, g * g, vec.META_LEN, sa["trained"], A, sa["others"], len(self.others), ptr(a_act), ptr(a_lp), ptr(a_val),
-            ptr(o_act), sa["lut"], sa["team1"], ptr(self.grid_codes[sl]), ptr(self.metadata_states[sl]), ptr(self.actions[sl]),
-            ptr(self.logprobs[sl]), ptr(self.values[sl]), ptr(self._env_actions), vec.device.index,
-            C.c_void_p(torch.cuda.current_stream(vec.device).cuda_stream))
-        if rc != 0:
-            raise _abi.CtfLibraryError("ctf_rollout_store_step: " + (sa["lib"].ctf_policy_last_error() or b"").decode())
+        _abi.call(sa["lib"], "ctf_rollout_store_step",
+                  ptr(codes), ptr(meta), E, N, g * g, vec.META_LEN, sa["trained"], A, sa["others"], len(self.others), ptr(a_act), ptr(a_lp), ptr(a_val),
+                  ptr(o_act), sa["lut"], sa["team1"], ptr(self.grid_codes[sl]), ptr(self.metadata_states[sl]), ptr(self.actions[sl]),
+                  ptr(self.logprobs[sl]), ptr(self.values[sl]), ptr(self._env_actions), vec.device.index, _abi.stream_ptr(vec.device))
 
     def preallocate(self, agent, opponent):
         """The observation part of the rollout buffer (29 GB of codes for 65 536 envs x 500 steps), allocated on the first collect

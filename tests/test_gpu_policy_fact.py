@@ -262,3 +262,29 @@ def test_view_gemm_equals_the_float64_product_of_its_bf16_operands(rows, kv):
     libm = torch.mm(a, w.t().contiguous(), out_dtype=torch.float32)
     assert float((libm.double() - want).abs().max()) < 2e-3
     assert lib.ctf_policy_view_gemm(C.c_void_p(a.data_ptr()), C.c_void_p(w.data_ptr()), rows, 100, C.c_void_p(out.data_ptr()), 0, None) != 0
+
+
+def test_the_native_view_gemm_switch_gives_the_library_paths_view_product():
+    """native_view_gemm = True: the factored path's view product by ctf_policy_view_gemm instead of the library's GEMM.  Its yview is held
+    to the bound the library's is held to above (test_factored_fc1_matches_its_float64_emulation: 5e-3 at most, 1e-5 on average from
+    the float64 product of the same bf16 operands), and fc1's output lies within one bf16 spacing plus twice that bound of the default
+    path's — two float32 sums of the same products, each rounded once."""
+    rng = np.random.default_rng(64)
+    g, c, n, e, sel = 15, 14, 8, 64, [4, 5, 6, 7]
+    m, p2 = 2 * n + 6, (g - 4) ** 2
+    codes, cells = team_codes(rng, e, n, g, c)
+    metas = rng.random((e, n, m)).astype(np.float16)
+    net = fill_(native.CtfPolicyNative(9, c, g, m)).cuda()
+    dev = lambda a: torch.tensor(a, device="cuda")
+    want_y1 = net.fc1_from_codes_factored(dev(codes), dev(metas), sel, dev(cells)).double().cpu()
+    net.native_view_gemm = True
+    y1 = net.fc1_from_codes_factored(dev(codes), dev(metas), sel, dev(cells)).double().cpu()
+    b = net._act_bufs[("fact", e, len(sel), 0)]
+    order = native.act_column_order(g, m)[:b["kv"]]
+    view = b["view"].double().cpu()
+    w = bf16(net.fc1.weight.detach().cpu().double() * S)[:, :32 * p2]
+    yv = torch.zeros((e, 32 * p2), dtype=torch.float64)
+    yv[:, order[order >= 0]] = view[:, order >= 0]
+    dg = (b["yview"].double().cpu() - yv @ w.T).abs()
+    assert float(dg.max()) < 5e-3 and float(dg.mean()) < 1e-5
+    assert bool(((y1 - want_y1).abs() <= ulp_bf16(want_y1) + 1e-2).all()), float((y1 - want_y1).abs().max())

@@ -401,6 +401,43 @@ def test_training_forward_through_the_native_front_gives_the_stock_paths_outputs
     print("relative gradient error against float32 (stock bf16 path, native front):", report)
 
 
+@pytest.mark.parametrize("flags", [dict(fused_backward=False), dict(native_wgrad=False), dict(native_fc1_wgrad=True)], ids=lambda f: next(iter(f)))
+def test_training_step_through_the_backward_paths_behind_the_class_switches(flags):
+    """The paths of a training step that the default switches do not take — the conv front's backward as three launches
+    (ctf_policy_front_dgrad + ctf_policy_front_wgrad), with the library's weight gradients (native_wgrad = False), fc1's weight gradient
+    by ctf_policy_linear_wgrad without a bias — at the smallest shipped shape, held to what the test above asks of the default path:
+    as close to the float32 network's gradients as the stock bf16 path is."""
+    g, c, n, b = 11, 8, 4, 777
+    rng = np.random.default_rng(g)
+    m = 2 * n + 6
+    codes = (rng.integers(0, c, (b, g, g)).astype(np.uint8) * (rng.random((b, g, g)) < 0.3)).astype(np.uint8)
+    codes.reshape(b, -1)[np.arange(b), rng.integers(0, g * g, b)] |= 128
+    codes_t = torch.tensor(codes, device="cuda")
+    meta_t = torch.tensor(rng.random((b, m)).astype(np.float16), device="cuda")
+    net = fill_(native.CtfPolicyNative(9, c, g, m)).cuda()
+    weight = torch.tensor(rng.standard_normal((b, 10)), device="cuda", dtype=torch.float32)
+
+    def grads(native_training, dtype=torch.bfloat16):
+        net.native_training, net.compute_dtype = native_training, dtype
+        net.zero_grad()
+        value, logits = net(codes_t, meta_t.float())
+        loss = (torch.cat((logits, value), dim=1) * weight).sum() / b
+        loss.backward()
+        return loss.item(), logits.detach().clone(), {k: q.grad.detach().clone() for k, q in net.named_parameters()}
+
+    _, _, gf = grads(False, torch.float32)
+    l0, lg0, g0 = grads(False)
+    for k, v in flags.items():
+        setattr(net, k, v)
+    l1, lg1, g1 = grads(True)
+    assert bool(((lg0 - lg1).abs() <= 4e-2 + 2.0 ** -7 * lg0.abs()).all()) and abs(l0 - l1) <= 2e-2 * max(1.0, abs(l0))
+    for k in gf:
+        den = max(float(gf[k].norm()), 1e-12)
+        e_stock, e_native = float((g0[k] - gf[k]).norm()) / den, float((g1[k] - gf[k]).norm()) / den
+        print(k, "relative gradient error against float32 (stock bf16 path, this path):", round(e_stock, 4), round(e_native, 4))
+        assert e_native <= 1.5 * e_stock + 1e-2 and e_native <= 5e-2, (k, e_stock, e_native)
+
+
 def test_native_path_fails_loudly_off_gpu():
     net = native.CtfPolicyNative(9, 14, 15, 22)
     with pytest.raises(pkg._abi.CtfLibraryError):

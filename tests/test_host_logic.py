@@ -219,3 +219,123 @@ def test_device_side_weight_layouts_equal_their_host_side_definitions():
         for name, (ref, parts, scale) in want.items():
             got = take(parts, maps[name], scale)
             assert got.shape == np.asarray(ref).shape and np.array_equal(got, np.asarray(ref, np.float32)), name
+
+
+# -- policy_native's module-level input checks and placement search (no device) -----------------------------------------------------
+class _FakeCuda:
+    """What the checks read of a tensor, with ``is_cuda`` True: a CPU tensor fails every check on its device alone."""
+
+    def __init__(self, t):
+        self.is_cuda, self.dtype, self.shape, self.is_contiguous = True, t.dtype, t.shape, t.is_contiguous
+
+
+CODES_ENGG = "codes must be a contiguous uint8 CUDA tensor [E, N, G, G]"
+CODES_BGG = "codes must be a contiguous uint8 CUDA tensor [B, G, G]"
+META_ENM = "meta must be a contiguous float16 CUDA tensor [E, N, M]"
+META_BM = "meta must be a contiguous float16 CUDA tensor [B, M]"
+SELF_CELLS = "self_cells must be a contiguous int16 CUDA tensor [E, N]"
+
+
+def _raises_exactly(text, fn, *args):
+    with pytest.raises(ValueError) as e:
+        fn(*args)
+    assert str(e.value) == text
+
+
+def test_policy_input_checks_keep_their_texts():
+    """The four texts are those of the parent commit's features_from_codes / _fact_run / features_train, as literals."""
+    import torch
+
+    native = importlib.import_module("marl-ctf-development_amd.policy_native")
+    E, N, G, M = 3, 4, 11, 14
+    u8, f16, i16 = torch.uint8, torch.float16, torch.int16
+    good = torch.zeros((E, N, G, G), dtype=u8)
+    bad_codes = [good.to(torch.int8), torch.zeros((E, N, G, G + 1), dtype=u8), torch.zeros((E, N, G), dtype=u8),
+                 torch.zeros((E, N, G, 2 * G), dtype=u8)[..., ::2]]
+    for t in [good] + bad_codes:  # a CPU tensor: refused whatever else holds
+        _raises_exactly(CODES_ENGG, native._check_codes, t, G, "E, N")
+    native._check_codes(_FakeCuda(good), G, "E, N")
+    for t in bad_codes:
+        _raises_exactly(CODES_ENGG, native._check_codes, _FakeCuda(t), G, "E, N")
+    good_b = torch.zeros((7, G, G), dtype=u8)
+    native._check_codes(_FakeCuda(good_b), G, "B")
+    for t in (good_b, _FakeCuda(good), _FakeCuda(good_b.to(torch.int32)), _FakeCuda(torch.zeros((7, G, 2 * G), dtype=u8)[..., ::2])):
+        _raises_exactly(CODES_BGG, native._check_codes, t, G, "B")
+
+    meta = torch.zeros((E, N, M), dtype=f16)
+    native._check_meta(_FakeCuda(meta), (E, N, M), "E, N")
+    for t in (meta, _FakeCuda(meta.float()), _FakeCuda(meta[:, :, :-1]), _FakeCuda(torch.zeros((E, N + 1, M), dtype=f16)),
+              _FakeCuda(torch.zeros((E, N, 2 * M), dtype=f16)[..., ::2])):
+        _raises_exactly(META_ENM, native._check_meta, t, (E, N, M), "E, N")
+    meta_b = torch.zeros((7, M), dtype=f16)
+    native._check_meta(_FakeCuda(meta_b), (7, M), "B")
+    for t in (meta_b, _FakeCuda(meta_b.double()), _FakeCuda(meta), _FakeCuda(torch.zeros((7, 2 * M), dtype=f16)[:, ::2])):
+        _raises_exactly(META_BM, native._check_meta, t, (7, M), "B")
+
+    cells = torch.zeros((E, N), dtype=i16)
+    native._check_self_cells(_FakeCuda(cells), E, N)
+    for t in (None, cells, _FakeCuda(cells.to(torch.int32)), _FakeCuda(cells[:, :-1]), _FakeCuda(torch.zeros((E, 2 * N), dtype=i16)[:, ::2])):
+        _raises_exactly(SELF_CELLS, native._check_self_cells, t, E, N)
+
+
+def test_agent_list_takes_every_form_of_agent_idx():
+    import torch
+
+    native = importlib.import_module("marl-ctf-development_amd.policy_native")
+    for idx in ([4, 0, 7], (4, 0, 7), np.array([4, 0, 7]), np.array([4, 0, 7], np.int8), torch.tensor([4, 0, 7]), torch.tensor([4, 0, 7], dtype=torch.int32)):
+        sel, arr = native._agent_list(idx)
+        assert sel == [4, 0, 7] and all(type(i) is int for i in sel)
+        assert list(arr) == [4, 0, 7] and len(arr) == 3 and arr._type_ is __import__("ctypes").c_int32
+    sel, arr = native._agent_list([])
+    assert sel == [] and len(arr) == 0
+
+
+class _Candidate:
+    pass
+
+
+def _run_search(native, times, tries, ratio, oom_at=None):
+    """_search_placement over stand-in candidates whose times come from ``times`` -> (index of the kept one, the times it returns,
+    candidates made, the most candidates alive at a call of make)."""
+    import gc
+    import weakref
+
+    import torch
+
+    made, alive_at_make, feed = [], [], iter(times)
+
+    def make():
+        gc.collect()
+        alive_at_make.append(sum(r() is not None for r in made))
+        if oom_at is not None and len(made) == oom_at:
+            raise torch.cuda.OutOfMemoryError("stand-in")
+        c = _Candidate()
+        made.append(weakref.ref(c))
+        return c
+
+    best, got = native._search_placement(make, lambda c: next(feed), tries, ratio)
+    return [r() for r in made].index(best), got, len(made), max(alive_at_make)
+
+
+def test_placement_search_with_injected_timings():
+    """Every expectation is the parent commit's loop (the one of _fact_run, which _features_tuned repeated) run by hand:
+        times = [t(first)];  while len(times) < tries and max(times) < ratio * min(times):  make (OutOfMemoryError: stop), time,
+        the new one is kept only when STRICTLY faster than all before, the other is released.
+    1. 1.08, [1.0, 1.01, 1.2]: 1.0 < 1.08 -> second, not faster; 1.01 < 1.08 -> third, not faster; 1.2 >= 1.08: stop.  First kept.
+    2. [1.2, 1.0]: 1.2 < 1.296 -> second, faster: kept; 1.2 >= 1.08: stop.
+    3. eight equal times: 1.0 < 1.08 every time, nothing ever strictly faster: the try limit ends it, first kept.
+    4. make raises on its second call: the search ends with the first buffer and its one time.
+    And the two sites' constants differ in effect: [1.0, 1.09, 1.11] ends after two candidates at 1.08 but after three at 1.1."""
+    native = importlib.import_module("marl-ctf-development_amd.policy_native")
+    assert _run_search(native, [1.0, 1.01, 1.2], 8, 1.08)[:3] == (0, [1.0, 1.01, 1.2], 3)
+    assert _run_search(native, [1.2, 1.0], 8, 1.08)[:3] == (1, [1.2, 1.0], 2)
+    assert _run_search(native, [1.0] * 9, 8, 1.08)[:3] == (0, [1.0] * 8, 8)
+    assert _run_search(native, [1.0] * 13, 12, 1.1)[:3] == (0, [1.0] * 12, 12)
+    assert _run_search(native, [1.0, 0.5], 8, 1.08, oom_at=1)[:3] == (0, [1.0], 1)
+    assert _run_search(native, [1.0, 1.09, 1.11], 8, 1.08)[:3] == (0, [1.0, 1.09], 2)
+    assert _run_search(native, [1.0, 1.09, 1.11], 12, 1.1)[:3] == (0, [1.0, 1.09, 1.11], 3)
+    # a tie keeps the earlier buffer; a later, strictly faster one replaces it
+    assert _run_search(native, [1.0, 1.0, 0.99, 2.0], 8, 1.08)[:3] == (2, [1.0, 1.0, 0.99, 2.0], 4)
+    # the loser has gone back before the next candidate is made: only the best so far is alive then (two held at most)
+    for times in ([1.0, 1.01, 1.02, 1.03, 2.0], [1.05, 1.04, 1.03, 1.02, 0.5]):
+        assert _run_search(native, times, 8, 1.08)[3] == 1
