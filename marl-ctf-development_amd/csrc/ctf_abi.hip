@@ -1,7 +1,8 @@
 // ctf_abi.hip — host side of the C ABI declared in include/ctf_env.h.
 //
 // Owns the device-side SoA state of one handle (one per GPU / shard), validates the config, derives
-// the device constant block and enqueues the kernels of ctf_kernels.hip on the caller's HIP stream.
+// the device constant block and enqueues the kernels of the other translation units (ctf_launch.h) on
+// the caller's HIP stream.
 // No torch, no C++ types across the boundary, no CPU implementation of the path.
 #include <hip/hip_runtime.h>
 
@@ -17,28 +18,8 @@
 #include "ctf_device.h"
 #include "ctf_device_scope.h"
 #include "ctf_harvest.h"
+#include "ctf_launch.h"
 #include "ctf_snapshot.h"
-
-extern "C" hipError_t ctf_launch_seed(const DevCfg&, const DevPtrs&, const uint64_t*, const uint64_t*, hipStream_t);
-extern "C" hipError_t ctf_launch_reset(const DevCfg&, const DevPtrs&, const uint8_t*, int, hipStream_t);
-extern "C" hipError_t ctf_launch_step(const DevCfg&, const DevPtrs&, const int8_t*, float*, double*, uint8_t*, uint32_t, int, hipStream_t);
-extern "C" int ctf_step_blocks(const DevCfg&);
-extern "C" int ctf_observe_uses_tiles(const DevCfg&, const uint8_t*);
-extern "C" hipError_t ctf_launch_observe(const DevCfg&, const DevPtrs&, uint8_t*, uint16_t*, uint32_t, int, hipStream_t);
-extern "C" hipError_t ctf_launch_observe_codes(const DevCfg&, const DevPtrs&, uint8_t*, uint16_t*, uint16_t*, uint32_t, int, hipStream_t);
-extern "C" hipError_t ctf_launch_random_actions(const DevCfg&, int8_t*, uint64_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t ctf_launch_import_rng(const DevCfg&, const DevPtrs&, const uint32_t*, const uint32_t*, int, int, hipStream_t);
-extern "C" hipError_t ctf_launch_export_rng(const DevCfg&, const DevPtrs&, uint32_t*, uint32_t*, int, int, hipStream_t);
-extern "C" hipError_t ctf_launch_rng_refill(const DevCfg&, const DevPtrs&, int, int, int, hipStream_t);
-extern "C" hipError_t ctf_launch_get_counters(const DevCfg&, const DevPtrs&, unsigned long long*, hipStream_t);
-extern "C" hipError_t ctf_launch_set_counters(const DevCfg&, const DevPtrs&, const unsigned long long*, hipStream_t);
-extern "C" int ctf_step_observe_one_launch(const DevCfg&, const uint8_t*);
-extern "C" hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, const int8_t*, float*, double*, uint8_t*, uint32_t, uint8_t*, uint16_t*,
-                                              uint32_t, uint32_t*, uint64_t, hipStream_t);
-extern "C" hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t*, int32_t*, int32_t*, hipStream_t);
-extern "C" hipError_t ctf_launch_save_states(const SnapLayout&, const int32_t*, int, uint8_t*, hipStream_t);         // ctf_snapshot.hip
-extern "C" hipError_t ctf_launch_load_states(const SnapLayout&, const uint8_t*, const int32_t*, int, hipStream_t);
-extern "C" hipError_t ctf_launch_harvest(const HarvestArgs&, const int32_t*, int, const uint8_t*, uint32_t, int64_t*, hipStream_t);  // ctf_harvest.hip
 
 struct ctf_env {
     ctf_config cfg;
@@ -341,12 +322,15 @@ extern "C" int ctf_reset(ctf_env* h, const uint8_t* mask_dev, void* stream) {
 extern "C" int ctf_step(ctf_env* h, const int8_t* actions, float* rw32, double* rw64, uint8_t* done, uint32_t flags, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
     DeviceScope guard(h->device);
-    HIP_TRY(ctf_launch_step(h->d, h->p, actions, rw32, rw64, done, flags, 1, (hipStream_t)stream));
+    HIP_TRY(ctf_launch_step(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, 1, (hipStream_t)stream));
     return CTF_OK;
 }
 
 static uint32_t resolve_reverse(const ctf_env* h, uint32_t reverse_mask) {
     return reverse_mask == CTF_REVERSE_DEFAULT ? (uint32_t)h->d.default_reverse : (reverse_mask & ((1u << h->d.N) - 1u));
+}
+static RenderArgs render_args(const ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask) {
+    return RenderArgs{obs, meta, resolve_reverse(h, reverse_mask), h->sync, h->spin_ticks};
 }
 
 extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, void* stream) {
@@ -354,7 +338,7 @@ extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t re
     if (!obs && !meta) return CTF_OK;
     DeviceScope guard(h->device);
     h->d.obs_store_nt = store_hint(h);
-    HIP_TRY(ctf_launch_observe(h->d, h->p, obs, meta, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
+    HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, meta, reverse_mask), h->n_cus, (hipStream_t)stream));
     return CTF_OK;
 }
 
@@ -385,14 +369,14 @@ extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, 
     // env-steps/s, profiles/r03_side_stream_ablation.md.)
     if (ctf_step_observe_one_launch(h->d, obs)) {
         h->d.obs_store_nt = store_hint(h);
-        HIP_TRY(ctf_launch_step_observe(h->d, h->p, actions, rw32, rw64, done, flags, obs, meta, resolve_reverse(h, reverse_mask), h->sync,
-                                        h->spin_ticks, (hipStream_t)stream));
+        HIP_TRY(ctf_launch_step_observe(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, render_args(h, obs, meta, reverse_mask),
+                                        (hipStream_t)stream));
         return CTF_OK;
     }
-    HIP_TRY(ctf_launch_step(h->d, h->p, actions, rw32, rw64, done, flags, 1, (hipStream_t)stream));
+    HIP_TRY(ctf_launch_step(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, 1, (hipStream_t)stream));
     if (obs || meta) {
         h->d.obs_store_nt = store_hint(h);
-        HIP_TRY(ctf_launch_observe(h->d, h->p, obs, meta, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, meta, reverse_mask), h->n_cus, (hipStream_t)stream));
     }
     return CTF_OK;
 }
@@ -565,11 +549,11 @@ extern "C" int ctf_host_step(ctf_env* h, const int8_t* actions, const uint32_t* 
         HIP_TRY(ctf_launch_rng_refill(d, h->p, 0, 1, 1, st));
     }
     if (actions)
-        HIP_TRY(ctf_launch_step(d, h->p, (const int8_t*)(hd + L.actions), nullptr, (double*)(hd + L.rw64), hd + L.done_status, flags,
+        HIP_TRY(ctf_launch_step(d, h->p, StepArgs{(const int8_t*)(hd + L.actions), nullptr, (double*)(hd + L.rw64), hd + L.done_status, flags},
                                 1, st));
     if (obs || meta)
-        HIP_TRY(ctf_launch_observe(d, h->p, obs ? hd + L.obs : nullptr, meta ? (uint16_t*)(hd + L.meta) : nullptr,
-                                   resolve_reverse(h, reverse_mask), h->n_cus, st));
+        HIP_TRY(ctf_launch_observe(d, h->p, render_args(h, obs ? hd + L.obs : nullptr, meta ? (uint16_t*)(hd + L.meta) : nullptr, reverse_mask),
+                                   h->n_cus, st));
     hipLaunchKernelGGL(k_host_pack, dim3(1), dim3(256), 0, st, d, h->p, hd, L, py_out ? (uint32_t*)(hd + L.py_out) : nullptr,
                        np_out ? (uint32_t*)(hd + L.np_out) : nullptr);
     HIP_TRY(hipGetLastError());

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctf_harvest.h"
+#include "ctf_launch.h"
 
 #define HV_WAVE 64
 #define HV_THREADS 256

@@ -1,17 +1,23 @@
 // ctf_kernels.hip — hand-written gfx950 (CDNA4) kernels of the batched GridworldCtf hot path.
 //
-//   k_seed            twin MT19937 seeding per env (CPython init_by_array / NumPy init_genrand)
 //   k_reset           GridworldCtf.reset()                       (reference gridworld_ctf.py:383-477)
-//   k_step            GridworldCtf.step(actions)                 (reference gridworld_ctf.py:849-918)
-//   k_observe         standardise_state + get_env_metadata, all agents (gridworld_ctf.py:975-1069)
+//   k_step            GridworldCtf.step(actions)                 (reference gridworld_ctf.py:849-918); its tail blocks
+//                     regenerate the MT19937 rings (ctf_ring_dev.h)
+//   k_observe         standardise_state + get_env_metadata, all agents (gridworld_ctf.py:975-1069), one wave per env at a time
+//   k_observe_tiles   the same render as one-shot 8 KiB tiles of the flat buffer (the default where it applies)
+//   k_step_observe    k_step and k_observe_tiles in ONE launch (opt-in) — why step and render share this translation unit
+//   k_observe_codes   the compact observation: one byte per (agent, cell)
+//   k_export_counters bulk export of the evaluation counters
 //   k_random_actions  synthetic Philox4x32-10 action stream for bench / tests
+// and their launchers (ctf_launch.h).  Seeding, the bulk ring refill and the generators' import / export: ctf_rng.hip.
 //
 // Integer / byte work, HBM-bound: no MFMA anywhere.  Wavefront = 64 lanes is assumed throughout.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
-#include "ctf_device.h"
+#include "ctf_launch.h"
 // Profiling-only phase trace of the step kernel (tools/trace_step.py): lane 0 of every block stamps the 100 MHz wall clock at
 // fixed points (0 start, 1 staged, 7 hit bits, 5 ring, 6 shuffle 1, 8/9/10 + 3 k act / tagging / metrics of turn k, 32 turns
 // done, 33 shuffle 2, 34 stepped, 2 barrier, 3 written back, 4 end); never defined in the shipped build.
@@ -25,9 +31,7 @@ __device__ unsigned long long g_step_trace[8192][40];
 #endif
 #define CTF_STAMP(k) do { if (((STEP_TRACE_MASK >> (k)) & 1ull) && threadIdx.x == 0 && blockIdx.x < 8192) g_step_trace[blockIdx.x][(k)] = wall_clock64(); } while (0)
 #endif
-#include "ctf_step_core.h"
-
-#define WAVE 64
+#include "ctf_ring_dev.h"  // (and through it ctf_step_core.h: both after CTF_STAMP)
 
 // ------------------------------------------------------------------------------------------------
 // small helpers (fdiv, cheb, the SGPR-pinned config lookups, MT19937: ctf_step_core.h / ctf_mt.h)
@@ -57,64 +61,6 @@ __device__ __forceinline__ uint16_t f64_to_f16(double d) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// seeding
-// ------------------------------------------------------------------------------------------------
-__device__ void mt_init_genrand(uint32_t* mt, uint32_t s) {
-    mt[0] = s;
-    uint32_t prev = s;
-    for (int i = 1; i < CTF_MT_N; i++) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        mt[i] = prev;
-    }
-}
-__device__ void mt_init_by_array(uint32_t* mt, const uint32_t* key, int len) {
-    mt_init_genrand(mt, 19650218u);
-    int i = 1, j = 0;
-    uint32_t prev = mt[0];
-    for (int k = CTF_MT_N > len ? CTF_MT_N : len; k; k--) {
-        prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
-        mt[i] = prev;
-        i++; j++;
-        if (i >= CTF_MT_N) { mt[0] = prev; i = 1; }
-        if (j >= len) j = 0;
-    }
-    for (int k = CTF_MT_N - 1; k; k--) {
-        prev = (mt[i] ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;
-        mt[i] = prev;
-        i++;
-        if (i >= CTF_MT_N) { mt[0] = prev; i = 1; }
-    }
-    mt[0] = 0x80000000u;
-}
-
-// py_seeds / np_seeds: device arrays [E].  After this (and the k_rng_refill(init) launch that follows it), env e ==
-// random.seed(py) ; np.random.seed(np) (MT19937 mode: ring 0 = the seeded state, position 624, as CPython / NumPy hold it), or
-// its two streams are the counter streams of these seeds at word 0 (counter mode).
-extern "C" __global__ void k_seed(DevCfg cfg, DevPtrs p, const uint64_t* py_seeds, const uint64_t* np_seeds) {
-    int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= cfg.n_envs) return;
-    uint32_t* a_py = p.mt_py + (size_t)e * 2 * CTF_MT_N;
-    uint32_t* a_np = p.mt_np + (size_t)e * 2 * CTF_MT_N;
-    const uint64_t ps = py_seeds[e], ns = np_seeds[e];
-    if (cfg.rng_mode == CTF_RNG_COUNTER) {
-        for (unsigned long long blk = 0; blk < CTF_MT_N / 4; blk++) {
-            ctr_block(ps, blk, 0u, a_py + 4 * blk);
-            ctr_block(ns, blk, 1u, a_np + 4 * blk);
-        }
-        unsigned long long* ctr = p.rngctr + 6 * (size_t)e;
-        ctr[0] = 0; ctr[2] = 0; ctr[4] = ps; ctr[5] = ns;  // ring 0 of either stream starts at word 0
-        p.rngpos[2 * e + 0] = CTF_RP_MAKE(0, 0);
-        p.rngpos[2 * e + 1] = CTF_RP_MAKE(0, 0);
-    } else {
-        uint32_t key[2] = {(uint32_t)ps, (uint32_t)(ps >> 32)};
-        mt_init_by_array(a_py, key, key[1] ? 2 : 1);
-        mt_init_genrand(a_np, (uint32_t)ns);
-        p.rngpos[2 * e + 0] = CTF_RP_MAKE(CTF_MT_N, 0);  // both generators start exhausted: the first draw comes from the next block
-        p.rngpos[2 * e + 1] = CTF_RP_MAKE(CTF_MT_N, 0);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // reset
 // ------------------------------------------------------------------------------------------------
 // One 64-lane block per env; mask == nullptr resets every env.  init_perm is set only by ctf_create.
@@ -135,209 +81,6 @@ extern "C" __global__ void __launch_bounds__(WAVE) k_reset(DevCfg cfg, DevPtrs p
         for (int w = lane; w < CTF_N_METRICS * cfg.N; w += WAVE) m[w] = 0;
         // visitation: reset_record flagged the base maps as zero and emptied the log — nothing to clear
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// ring regeneration by one wave (ctf_mt.h): used by the tail blocks of k_step and by k_rng_refill
-// ------------------------------------------------------------------------------------------------
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-#define RNG_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xC07F); \
-        __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-// ---- the digests of ctf_mt.h as ONE WAVE makes them, from a block's OUTPUT words (tempered, or as they are in counter mode) in
-// LDS: the hit bits of 64 positions are one ballot, a nibble / top-byte dword is a handful of LDS reads.  (ring_digest /
-// ring_link in ctf_mt.h are the same arithmetic one word at a time: the step kernel's safety net and the host simulator use
-// those, and tests run both against each other through CTF_RNG_REFILL_EVERY.)
-__device__ __forceinline__ void wave_digest(int lane, const uint32_t* T, const RingPtrs& p, int r, const RingParams& q) {
-    if (q.stream == 1) {
-        uint32_t* hit = p.hit + r * CTF_HB_DW;
-        uint32_t t0[10], t1[10];
-#pragma unroll
-        for (int c = 0; c < 10; c++) {  // 624 positions = 10 x 64 (the last 16 lanes of the last pass idle): the reads first
-            const int i = 64 * c + lane;
-            t0[c] = T[i < CTF_MT_N ? i : 0];
-            t1[c] = T[i + 1 < CTF_MT_N ? i + 1 : 0];
-        }
-#pragma unroll
-        for (int c = 0; c < 10; c++) {
-            const int i = 64 * c + lane;
-            const unsigned long long m = __ballot(i < CTF_MT_N - 1 && mt_lt53(t0[c] >> 5, t1[c] >> 6, q.th, q.tl));
-            if (lane < 2 && 2 * c + lane < (CTF_MT_N + 31) / 32) hit[2 * c + lane] = (uint32_t)(m >> (32 * lane));
-        }
-        uint32_t* nib = p.nib + r * CTF_NB_DW;
-        const u32x4_t* T4 = (const u32x4_t*)T;
-#pragma unroll
-        for (int it = 0; it < 2; it++) {  // 78 dwords of 8 nibbles
-            const int d = lane + 64 * it;
-            if (d < CTF_MT_N / 8) {
-                const u32x4_t a = T4[2 * d], b = T4[2 * d + 1];
-                nib[d] = (a.x & 15u) | ((a.y & 15u) << 4) | ((a.z & 15u) << 8) | ((a.w & 15u) << 12) | ((b.x & 15u) << 16) | ((b.y & 15u) << 20) |
-                         ((b.z & 15u) << 24) | ((b.w & 15u) << 28);
-            }
-        }
-    } else {
-        uint32_t* top = p.top + r * CTF_P8_DW;
-        const u32x4_t* T4 = (const u32x4_t*)T;
-#pragma unroll
-        for (int it = 0; it < 3; it++) {  // 156 dwords of 4 top bytes
-            const int d = lane + 64 * it;
-            if (d < CTF_MT_N / 4) {
-                const u32x4_t a = T4[d];
-                top[d] = (a.x >> 24) | ((a.y >> 24) << 8) | ((a.z >> 24) << 16) | ((a.w >> 24) << 24);
-            }
-        }
-    }
-}
-// Tc: outputs of ring c (only words 608 .. 623 are read), To: outputs of its successor ring
-__device__ __forceinline__ void wave_link(int lane, const uint32_t* Tc, const uint32_t* To, const RingPtrs& p, int c, const RingParams& q) {
-    if (q.stream == 1) {
-        uint32_t* hc = p.hit + c * CTF_HB_DW;
-        constexpr int P0 = (CTF_MT_N >> 5) * 32;  // 608: the first position of dword 19
-        uint32_t w0[4], w1[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {  // positions 608 .. 863, counted from ring c's start (dwords 19 .. 26: the array ends at 25)
-            const int pc = P0 + 64 * k + lane;
-            w0[k] = pc < CTF_MT_N ? Tc[pc] : To[pc - CTF_MT_N];
-            w1[k] = pc + 1 < CTF_MT_N ? Tc[pc + 1] : To[pc + 1 - CTF_MT_N];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const unsigned long long m = __ballot(mt_lt53(w0[k] >> 5, w1[k] >> 6, q.th, q.tl));
-            const int d = (CTF_MT_N >> 5) + 2 * k + lane;
-            if (lane < 2 && d < CTF_HB_DW) hc[d] = (uint32_t)(m >> (32 * lane));
-        }
-        uint32_t* nc = p.nib + c * CTF_NB_DW;
-        if (lane < CTF_NB_MIRROR / 8) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) v |= (To[8 * lane + k] & 15u) << (4 * k);
-            nc[CTF_MT_N / 8 + lane] = v;
-        }
-    } else {
-        uint32_t* tc = p.top + c * CTF_P8_DW;
-        if (lane < CTF_P8_MIRROR / 4) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) v |= (To[4 * lane + k] >> 24) << (8 * k);
-            tc[CTF_MT_N / 4 + lane] = v;
-        }
-    }
-}
-// the block after `src` into `dst` (both LDS) by one wave: ring_next_block of ctf_mt.h with the three dependent chunks unrolled, every
-// chunk's LDS reads issued before its arithmetic
-__device__ __forceinline__ void wave_next_block(int lane, const uint32_t* src, uint32_t* dst, const RingParams& q) {
-    if (q.counter_mode) {
-#pragma unroll 1
-        for (int b = lane; b < CTF_MT_N / 4; b += WAVE) {
-            uint32_t o[4];
-            ctr_block(q.seed, (q.nbase + CTF_MT_N) / 4 + (unsigned long long)b, (uint32_t)q.stream, o);
-            ((u32x4_t*)dst)[b] = u32x4_t{o[0], o[1], o[2], o[3]};
-        }
-        RNG_WAVE_SYNC();
-        return;
-    }
-    constexpr int M = CTF_MT_N - 397;  // 227
-#pragma unroll
-    for (int chunk = 0; chunk < 3; chunk++) {
-        const int lo = chunk * M, hi = chunk == 2 ? CTF_MT_N - 1 : lo + M;  // [0, 227), [227, 454), [454, 623)
-        uint32_t x0[4], x1[4], m[4];
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int i = lo + lane + 64 * it, ic = i < hi ? i : lo;
-            x0[it] = src[ic];
-            x1[it] = src[ic + 1];
-            m[it] = chunk == 0 ? src[ic + 397] : dst[ic - M];
-        }
-#pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int i = lo + lane + 64 * it;
-            if (i < hi) dst[i] = mt_twist(x0[it], x1[it], m[it]);
-        }
-        if (chunk == 2 && lane == 0) dst[CTF_MT_N - 1] = mt_twist(src[CTF_MT_N - 1], dst[0], dst[396]);
-        RNG_WAVE_SYNC();
-    }
-}
-
-// One ring, one wave: the ring the consumer has left becomes the block after the current one, with its digests, and the current
-// ring is linked to it (mirror, hit bit of its last position).  src / dst: 2 x 624 words of the wave's LDS.  `init`: the CURRENT
-// ring's digests are made too (after a seed or a state import).  2.5 KB read, 2.5 KB + the digests written, every access of the
-// wave contiguous.
-#if STEP_TRACE
-#define RING_STAMP(k) CTF_STAMP(k)  // of a tail block's LAST ring (tools/trace_step.py)
-#else
-#define RING_STAMP(k) do { } while (0)
-#endif
-// the ring's words on their way into the wave (issued early: the previous ring of the same tail block is still being worked on)
-struct RingIn {
-    StreamFull st;
-    u32x4_t a, b, c;
-};
-__device__ __forceinline__ RingIn ring_fetch(const DevCfg& cfg, const DevPtrs& p, int e, int stream, uint32_t flag, int lane) {
-    RingIn in;
-    in.st.r = ring_ptrs(p, e, stream);
-    in.st.q = ring_params(cfg, p, e, stream);
-    // The flag says which ring is stale (the position word may be moving); only an init pass (flag 0) has to read the position word —
-    // the branch is uniform, and without it every regeneration would wait for that load before it can even address its ring: one
-    // more dependent memory round trip on a 5.65 us job.
-    const uint32_t uflag = (uint32_t)__builtin_amdgcn_readfirstlane((int)flag);  // (the same in every lane: one ring per wave)
-    if (uflag >= 2u) in.st.cur = 1u - (uflag - 2u);
-    else in.st.cur = ring_source(uflag, p.rngpos[2 * (size_t)e + stream]);
-    ring_counter_params(in.st.q, p, e, stream, in.st.cur);
-    const u32x4_t* gsrc = (const u32x4_t*)(in.st.r.raw + in.st.cur * CTF_MT_N);
-    constexpr int NQ = CTF_MT_N / 4;  // 156 quads: two full passes of the wave and 28 lanes of a third
-    in.a = gsrc[lane];
-    in.b = gsrc[lane + WAVE];
-    in.c = gsrc[lane + 2 * WAVE < NQ ? lane + 2 * WAVE : 0];
-    return in;
-}
-__device__ __forceinline__ void refill_ring(const DevCfg& cfg, const DevPtrs& p, int e, int stream, const RingIn& in, int lane, uint32_t* src,
-                                            uint32_t* dst, bool init) {
-    StreamFull st = in.st;
-    u32x4_t* gdst = (u32x4_t*)(st.r.raw + (1 - st.cur) * CTF_MT_N);
-    constexpr int NQ = CTF_MT_N / 4;
-    ((u32x4_t*)src)[lane] = in.a;
-    ((u32x4_t*)src)[lane + WAVE] = in.b;
-    if (lane + 2 * WAVE < NQ) ((u32x4_t*)src)[lane + 2 * WAVE] = in.c;
-    RING_STAMP(10);
-    RNG_WAVE_SYNC();
-    wave_next_block(lane, src, dst, st.q);
-    RING_STAMP(11);
-    {   // the new block's raw words leave; both LDS copies then become OUTPUT words (of ring c only what is looked at)
-        u32x4_t v[3];
-#pragma unroll
-        for (int it = 0; it < 3; it++) v[it] = ((const u32x4_t*)dst)[lane + WAVE * it < NQ ? lane + WAVE * it : 0];
-#pragma unroll
-        for (int it = 0; it < 3; it++) {
-            const int d = lane + WAVE * it;
-            if (d < NQ) {
-                gdst[d] = v[it];
-                ((u32x4_t*)dst)[d] = u32x4_t{ring_out(st.q, v[it].x), ring_out(st.q, v[it].y), ring_out(st.q, v[it].z), ring_out(st.q, v[it].w)};
-            }
-        }
-        if (init) {
-#pragma unroll
-            for (int it = 0; it < 3; it++) {
-                const int d = lane + WAVE * it;
-                if (d < NQ) {
-                    const u32x4_t w = ((const u32x4_t*)src)[d];
-                    ((u32x4_t*)src)[d] = u32x4_t{ring_out(st.q, w.x), ring_out(st.q, w.y), ring_out(st.q, w.z), ring_out(st.q, w.w)};
-                }
-            }
-        } else if (lane < 16) {
-            src[(CTF_MT_N >> 5) * 32 + lane] = ring_out(st.q, src[(CTF_MT_N >> 5) * 32 + lane]);
-        }
-    }
-    RNG_WAVE_SYNC();
-    RING_STAMP(12);
-    if (init) wave_digest(lane, src, st.r, (int)st.cur, st.q);
-    wave_digest(lane, dst, st.r, 1 - (int)st.cur, st.q);
-    RING_STAMP(13);
-    wave_link(lane, src, dst, st.r, (int)st.cur, st.q);
-    RING_STAMP(14);
-    if (lane == 0) {
-        ring_counter_store(st.q, p, e, stream, 1u - st.cur);
-        p.rngready[2 * (size_t)e + stream] = 1;
-    }
-    RNG_WAVE_SYNC();  // the LDS copies are reused by the wave's next ring
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -603,14 +346,11 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
        uint8_t* __restrict__ done_out, uint32_t flags, int n_step_blocks) {
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x;
-#ifndef STEP_TAIL_FIRST
-#define STEP_TAIL_FIRST 0  // 1 (measured, not shipped): the ring-regenerating blocks at the HEAD of the grid instead of its tail
-#endif
-    const int n_tail_blocks = (int)gridDim.x - n_step_blocks;
-    const int sb = STEP_TAIL_FIRST ? (int)blockIdx.x - n_tail_blocks : (int)blockIdx.x;  // this step block's index
-    if (STEP_TAIL_FIRST ? sb < 0 : sb >= n_step_blocks) {
-        // ---- a TAIL block (see tail_block): these start as step blocks retire — the LDS is full until then
-        tail_block(cfg, p, STEP_TAIL_FIRST ? (int)blockIdx.x : sb - n_step_blocks, lane, lds);
+    const int sb = (int)blockIdx.x;  // this step block's index
+    if (sb >= n_step_blocks) {
+        // ---- a TAIL block (see tail_block): these start as step blocks retire — the LDS is full until then.  (Tried: the tail
+        // blocks at the HEAD of the grid instead — not faster, profiles/r03_tail_block_ablation.txt.)
+        tail_block(cfg, p, sb - n_step_blocks, lane, lds);
         return;
     }
     STEP_STAMP(0);
@@ -635,13 +375,24 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
 //      instruction per 64 chunks.
 // Metadata rows (f16 [N][2N+6]) are assembled in LDS and leave as 8-byte stores.
 //
-// Per-wave LDS (bytes): [rec RS][mvals 96][meta staging][meta source LUT][bitmap]
+// ---- The per-wave LDS of the three renders (bytes).  Each kernel carves its own up by these sizes, in this order:
+//   k_observe        [rec RS][mvals 96][meta staging][meta source LUT][bitmap]
+//   k_observe_codes  [rec RS][mvals 96][meta staging][meta source LUT][grid GS][self cell u16[16]][maps 4 x (GGp + 4)]
+//   tile_render      [bitmap TILE / 8][rec RS][mvals 96][meta staging]          (its LUT is the host-built table in global memory)
 #define OBS_MV_BYTES 96
+#define OBS_TILE CTF_OBS_TILE
 __host__ __device__ inline int obs_meta_stage_bytes(int N, int M) { return (N * M * 2 + 15) & ~15; }
 __host__ __device__ inline int obs_bitmap_bytes(int obs_bytes) { return ((((obs_bytes + 31) / 32 + 1) * 4) + 15) & ~15; }
 __host__ __device__ inline int obs_meta_lut_bytes(int N, int M) { return (N * M + 15) & ~15; }
+__host__ __device__ inline int codes_map_stride(int GG) { return ((GG + 3) & ~3) + 4; }  // + 4: the funnel read's second dword
 __host__ __device__ inline int obs_wave_bytes(int RS, int N, int M, int obs_bytes) {
     return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_meta_lut_bytes(N, M) + obs_bitmap_bytes(obs_bytes);
+}
+__host__ __device__ inline int codes_wave_bytes(int GS, int RS, int GG, int N, int M) {
+    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_meta_lut_bytes(N, M) + GS + 32 + 4 * codes_map_stride(GG);
+}
+__host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
+    return OBS_TILE / 8 + RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M);
 }
 
 #ifndef OBS_TILES_DEFAULT
@@ -657,10 +408,6 @@ __host__ __device__ inline int obs_wave_bytes(int RS, int N, int M, int obs_byte
 //   bit0 no bit expansion, bit1 no chunk stores, bit2 no bitmap build, bit3 no metadata, bit4 metadata computed but not stored
 #ifndef OBS_ABLATE
 #define OBS_ABLATE 0
-#endif
-// experiment (G <= 16 only, results wrong beyond): no compiler-tracked load anywhere in the render loop
-#ifndef OBS_NODRAIN
-#define OBS_NODRAIN 0
 #endif
 
 template <int ALIGN>
@@ -774,9 +521,7 @@ __device__ __forceinline__ void obs_build_env(const DevCfg& cfg, const DevPtrs& 
     // ---- hot bits of every tile plane
     if (has_cells) {
         for (int w = lane; w < GW; w += WAVE) {
-#if !OBS_NODRAIN
             if (w >= WAVE) cells = ((const uint32_t*)(p.grid + (size_t)e * cfg.GS))[w];  // G > 16 only
-#endif
             int r = (int)fdiv((uint32_t)(w * 4), cfg.div_g), c = w * 4 - r * G;
             #pragma unroll
             for (int b = 0; b < 4; b++) {
@@ -904,18 +649,13 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
         e_end = min(lo + chunk, cfg.n_envs);
     }
     // the first env's state: ordinary loads; every later env's state arrives through the prefetch below
+    // (Tried: no compiler-tracked load anywhere in the render loop, these two as prefetches too — wrong results beyond G = 16
+    // and no timing recorded.)
     uint32_t recw = 0, cells = 0;
-#if OBS_NODRAIN
-    if (e_first >= e_end) return;
-    recw = obs_prefetch_dword((const uint32_t*)(p.rec + (size_t)e_first * cfg.RS) + rec_lane);
-    cells = obs_prefetch_dword((const uint32_t*)(p.grid + (size_t)e_first * cfg.GS) + grid_lane);
-    OBS_PREFETCH_DRAIN(recw, cells);
-#else
     if (e_first < e_end) {
         recw = ((const uint32_t*)(p.rec + (size_t)e_first * cfg.RS))[rec_lane];
         cells = ((const uint32_t*)(p.grid + (size_t)e_first * cfg.GS))[grid_lane];
     }
-#endif
 
     for (int e = e_first; e < e_end; e += e_stride) {
         obs_build_env(cfg, p, e, recw, cells, srec, mv, mstage, mlut, bits, slots, reverse_mask, lane, obs != nullptr, meta);
@@ -965,12 +705,7 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
                 cells = ((const uint32_t*)(p.grid + (size_t)(e + e_stride) * cfg.GS))[grid_lane];
             }
         } else if (e + e_stride < e_end) {
-#if OBS_NODRAIN
-            recw = obs_prefetch_dword((const uint32_t*)(p.rec + (size_t)(e + e_stride) * cfg.RS) + rec_lane);
-            OBS_PREFETCH_DRAIN(recw, cells);
-#else
             recw = ((const uint32_t*)(p.rec + (size_t)(e + e_stride) * cfg.RS))[rec_lane];
-#endif
         }
         __builtin_amdgcn_s_waitcnt(LGKM_ONLY);  // this env's LDS reads are done before the next env reuses the bitmap
         __builtin_amdgcn_wave_barrier();
@@ -995,13 +730,9 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
 // its own eighth of the buffer front to back, 0.306 -> 0.259 ms on the arena (profiles/r02_store_bw9_xcd.txt for the bare pattern).
 // Metadata rows: written by the wave whose tile holds an env's first byte.
 // Used when an env's block is a multiple of 16 bytes and >= one tile and the buffer is 16-byte aligned (ctf_launch_observe).
-#define OBS_TILE CTF_OBS_TILE
 #ifndef OBS_TILE_BLOCK_LDS
 #define OBS_TILE_BLOCK_LDS (10 * 1024)  // dynamic LDS of a k_observe_tiles block at least: 160 KiB / 10 KiB = 16 blocks (waves) per CU
 #endif
-__host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
-    return OBS_TILE / 8 + RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M);
-}
 
 // What a tile of k_step_observe waits for: the flags of the (one or two) step blocks of its envs (EPW = 1 << epw_shift envs each).
 struct TileWait {
@@ -1263,13 +994,7 @@ k_step_observe(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float*
 // A policy that consumes the codes directly (ctf_policy.hip) never needs the 14x larger one-hot block.
 // Per env a wave builds the (viewer team, reversed?) code maps that are in use (at most 4) in LDS; every agent's row is
 // its map plus the own-position bit: an output dword is two aligned dwords of the map funnel-shifted (v_alignbyte_b32).
-// The metadata rows leave in the same launch.  Per-wave LDS: obs_build_env's metadata scratch ...
-// ... and the metadata scratch of obs_build_env when the launch also writes the metadata rows:
-// [rec RS][mvals 96][meta staging][meta LUT][grid GS][self cell u16[16]][maps 4 x (GGp + 4)]
-__host__ __device__ inline int codes_map_stride(int GG) { return ((GG + 3) & ~3) + 4; }  // + 4: the funnel read's second dword
-__host__ __device__ inline int codes_wave_bytes(int GS, int RS, int GG, int N, int M) {
-    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_meta_lut_bytes(N, M) + GS + 32 + 4 * codes_map_stride(GG);
-}
+// The metadata rows leave in the same launch.  Per-wave LDS: see the size functions above k_observe.
 
 template <bool DWORDS>
 __global__ void __launch_bounds__(256) k_observe_codes(DevCfg cfg, DevPtrs p, uint8_t* __restrict__ codes,
@@ -1390,87 +1115,6 @@ extern "C" __global__ void k_export_counters(DevCfg cfg, DevPtrs p, int32_t* met
 }
 
 // ------------------------------------------------------------------------------------------------
-// the bulk ring refill (ctf_mt.h) and the hand-over of the generator states
-// ------------------------------------------------------------------------------------------------
-#define RNG_PAIRS_PER_WAVE 16  // (env, stream) pairs a wave looks after: their flags arrive in one load
-
-// One wave per ring to regenerate: the ring the consumer has left becomes the block after the current one, with its digests, and
-// the current ring is linked to it (mirror, hit bit of its last position).  Envs [e0, e0 + count).  `init`: every stream of
-// the range is treated as not ready and the CURRENT ring's digests are made first (after a seed or a state import).
-// Whole blocks, staged in LDS: 2.5 KB read, 2.5 KB + the digests written per ring, every access of a wave contiguous.
-extern "C" __global__ void __launch_bounds__(256) k_rng_refill(DevCfg cfg, DevPtrs p, int e0, int count, int init) {
-    __shared__ uint32_t sh[4][2 * CTF_MT_N];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    uint32_t* src = sh[wave];
-    uint32_t* dst = src + CTF_MT_N;
-    const int first = (blockIdx.x * 4 + wave) * RNG_PAIRS_PER_WAVE;  // pair t = env e0 + t / 2, stream t % 2
-    if (first >= 2 * count) return;
-    uint32_t flag = 1;
-    if (lane < RNG_PAIRS_PER_WAVE && first + lane < 2 * count) flag = init ? 0u : p.rngready[2 * (size_t)e0 + first + lane];
-    const bool todo = flag != 1u;
-    unsigned long long work = __ballot(todo);
-    while (work) {  // uniform
-        const int k = __ffsll((long long)work) - 1;
-        work &= work - 1;
-        const int t = first + k, e = e0 + (t >> 1), stream = t & 1;
-        refill_ring(cfg, p, e, stream, ring_fetch(cfg, p, e, stream, (uint32_t)__shfl((int)flag, k, WAVE), lane), lane, src, dst, init != 0);
-    }
-}
-
-// Standard form per env and generator: 624 state words + the position (0..624), as random.getstate()[1] /
-// np.random.get_state()[1:3] give them — which is what ring `cur` and the stream position ARE.  One block per env: block b
-// handles env e0 + b and record b of the arrays.  An import is followed by k_rng_refill(init) over the same envs.
-extern "C" __global__ void __launch_bounds__(256) k_import_rng(DevCfg cfg, DevPtrs p, const uint32_t* __restrict__ py,
-                                                               const uint32_t* __restrict__ np_, int e0) {
-    const int e = e0 + (int)blockIdx.x, t = threadIdx.x;
-    const uint32_t* src[2] = {py, np_};
-    uint32_t* dst[2] = {p.mt_py, p.mt_np};
-    for (int k = 0; k < 2; k++) {
-        if (!src[k]) continue;  // uniform
-        const uint32_t* in = src[k] + (size_t)blockIdx.x * (CTF_MT_N + 1);
-        uint32_t* out = dst[k] + (size_t)e * 2 * CTF_MT_N;
-        for (int i = t; i < CTF_MT_N; i += blockDim.x) out[i] = in[i];
-        if (t == 0) p.rngpos[2 * e + k] = CTF_RP_MAKE(in[CTF_MT_N] > CTF_MT_N ? CTF_MT_N : in[CTF_MT_N], 0);
-    }
-}
-extern "C" __global__ void __launch_bounds__(256) k_export_rng(DevCfg cfg, DevPtrs p, uint32_t* __restrict__ py, uint32_t* __restrict__ np_, int e0) {
-    const int e = e0 + (int)blockIdx.x, t = threadIdx.x;
-    uint32_t* dst[2] = {py, np_};
-    const uint32_t* src[2] = {p.mt_py, p.mt_np};
-    for (int k = 0; k < 2; k++) {
-        if (!dst[k]) continue;  // uniform
-        const uint32_t rp = p.rngpos[2 * e + k];
-        const uint32_t* in = src[k] + ((size_t)e * 2 + CTF_RP_CUR(rp)) * CTF_MT_N;
-        uint32_t* out = dst[k] + (size_t)blockIdx.x * (CTF_MT_N + 1);
-        for (int i = t; i < CTF_MT_N; i += blockDim.x) out[i] = in[i];
-        if (t == 0) out[CTF_MT_N] = CTF_RP_POS(rp);
-    }
-}
-// counter mode: (words consumed from the `random` stream, ... from the np.random stream) of every env
-extern "C" __global__ void k_get_counters(DevCfg cfg, DevPtrs p, unsigned long long* out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= cfg.n_envs) return;
-    for (int k = 0; k < 2; k++) {
-        const uint32_t rp = p.rngpos[2 * e + k];
-        out[2 * (size_t)e + k] = p.rngctr[6 * (size_t)e + 2 * k + CTF_RP_CUR(rp)] + CTF_RP_POS(rp);
-    }
-}
-// ... and the way back (a checkpoint restore; followed by k_rng_refill(init)): ring 0 = the block that holds word n
-extern "C" __global__ void k_set_counters(DevCfg cfg, DevPtrs p, const unsigned long long* in) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= cfg.n_envs) return;
-    unsigned long long* ctr = p.rngctr + 6 * (size_t)e;
-    for (int k = 0; k < 2; k++) {
-        const unsigned long long n = in[2 * (size_t)e + k], blk = n / CTF_MT_N;
-        ctr[2 * k] = blk * CTF_MT_N;
-        uint32_t* a = (k ? p.mt_np : p.mt_py) + (size_t)e * 2 * CTF_MT_N;
-        for (unsigned long long b = 0; b < CTF_MT_N / 4; b++) ctr_block(ctr[4 + k], blk * (CTF_MT_N / 4) + b, (uint32_t)k, a + 4 * b);
-        p.rngpos[2 * e + k] = CTF_RP_MAKE((uint32_t)(n - blk * CTF_MT_N), 0);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // synthetic actions: Philox4x32-10 (Salmon et al. 2011), one lane per (env, block of 8 agents)
 // ------------------------------------------------------------------------------------------------
 extern "C" __global__ void k_random_actions(DevCfg cfg, int8_t* actions, uint64_t seed, uint32_t step, uint32_t env_offset) {
@@ -1499,34 +1143,44 @@ extern "C" __global__ void k_random_actions(DevCfg cfg, int8_t* actions, uint64_
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (called from ctf_abi.hip)
+// launchers (ctf_launch.h; called from ctf_abi.hip)
 // ------------------------------------------------------------------------------------------------
-extern "C" hipError_t ctf_launch_seed(const DevCfg& cfg, const DevPtrs& p, const uint64_t* py, const uint64_t* np_, hipStream_t st) {
-    hipLaunchKernelGGL(k_seed, dim3((cfg.n_envs + 63) / 64), dim3(64), 0, st, cfg, p, py, np_);
-    return hipGetLastError();
+// ---- integer knobs of the environment (tests, profiling).  Read at every call unless said otherwise: tests flip them inside
+// one process.
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
 }
+static bool obs_xcd_knob() { return env_int("CTF_OBS_XCD", 1) != 0; }  // 0: launch-order tiles / plain grid-stride envs (profiling); default: XCD-contiguous
+static int obs_reserve_blocks() {  // read once
+    static const int v = env_int("CTF_OBS_RESERVE_BLOCKS", 0);
+    return v < 0 ? 0 : v;
+}
+// waves per block of the wave-per-env renders: 4 unless one env's LDS is so large that 4 of them would crowd the CU's LDS
+static int obs_waves_per_block(int per_wave) {
+    int wpb = 4;
+    while (wpb > 1 && wpb * per_wave > 40 * 1024) wpb >>= 1;
+    return wpb;
+}
+// run-time switches -> template arguments: f gets std::integral_constant values
+template <typename F>
+static void with_bool(bool b, F f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename F>
+static void with_step_variant(bool log_metrics, int w, F f) {  // f(METRICS, W)
+    with_bool(log_metrics, [&](auto m) {
+        if (w <= 1) f(m, std::integral_constant<int, 1>{});
+        else if (w == 2) f(m, std::integral_constant<int, 2>{});
+        else if (w == 4) f(m, std::integral_constant<int, 4>{});
+        else f(m, std::integral_constant<int, 8>{});
+    });
+}
+
 extern "C" hipError_t ctf_launch_reset(const DevCfg& cfg, const DevPtrs& p, const uint8_t* mask, int init_perm, hipStream_t st) {
     hipLaunchKernelGGL(k_reset, dim3(cfg.n_envs), dim3(WAVE), 0, st, cfg, p, mask, init_perm);
     return hipGetLastError();
-}
-template <bool METRICS, int W>
-static void launch_step_w(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64, uint8_t* done,
-                          uint32_t flags, bool with_tail, hipStream_t st) {
-    constexpr int EPW = WAVE / W;
-    const int nstep = (cfg.n_envs + EPW - 1) / EPW;
-    const int ntail = with_tail ? (2 * cfg.n_envs + STEP_TAIL_PAIRS - 1) / STEP_TAIL_PAIRS : 0;
-    const dim3 grid(nstep + ntail), block(WAVE);
-    size_t sh = (size_t)EPW * step_slot_bytes(cfg.GS, cfg.RS, cfg.N, METRICS);
-    if (sh < 2 * CTF_MT_N * 4) sh = 2 * CTF_MT_N * 4;  // a tail block stages two rings
-    hipLaunchKernelGGL((k_step<METRICS, W>), grid, block, sh, st, cfg, p, actions, rw32, rw64, done, flags, nstep);
-}
-template <bool METRICS>
-static void launch_step_m(int w, const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64,
-                          uint8_t* done, uint32_t flags, bool with_tail, hipStream_t st) {
-    if (w <= 1) launch_step_w<METRICS, 1>(cfg, p, actions, rw32, rw64, done, flags, with_tail, st);
-    else if (w == 2) launch_step_w<METRICS, 2>(cfg, p, actions, rw32, rw64, done, flags, with_tail, st);
-    else if (w == 4) launch_step_w<METRICS, 4>(cfg, p, actions, rw32, rw64, done, flags, with_tail, st);
-    else launch_step_w<METRICS, 8>(cfg, p, actions, rw32, rw64, done, flags, with_tail, st);
 }
 // lanes per env: the power of two that covers the larger opponents list (<= 8), so one tag pass per agent turn — and more
 // (up to 8) as long as the waves that makes stay within 8 per CU (half of what is resident at once): fewer envs per wave then,
@@ -1539,49 +1193,36 @@ static int step_lanes(const DevCfg& cfg) {
     if (cfg.step_lanes_override) w = cfg.step_lanes_override;  // profiling / test knob (CTF_STEP_W)
     return w;
 }
+// The step part of a grid of one-wave blocks: nstep step blocks (WAVE / w envs each), then ntail ring-regenerating blocks, and
+// the dynamic LDS they need.  A tail block stages two rings (4 992 bytes), which is MORE than the step blocks' slots whenever
+// w = 8 meets a small grid (8 slots of GS + RS + 128 bytes or so), so whether that floor holds WITHOUT tail blocks
+// (CTF_RNG_REFILL_EVERY=0) changes the launch: k_step has always taken it then, k_step_observe never.  Nothing reads the extra
+// bytes; both are kept as they were (`tail_lds_always`) because this shape is compared launch for launch with its history.
+struct StepShape {
+    int nstep, ntail;
+    size_t lds;
+};
+static StepShape step_shape(const DevCfg& cfg, int w, bool metrics, bool with_tail, bool tail_lds_always) {
+    const int epw = WAVE / w;
+    StepShape s;
+    s.nstep = (cfg.n_envs + epw - 1) / epw;
+    s.ntail = with_tail ? (2 * cfg.n_envs + STEP_TAIL_PAIRS - 1) / STEP_TAIL_PAIRS : 0;
+    s.lds = (size_t)epw * step_slot_bytes(cfg.GS, cfg.RS, cfg.N, metrics);
+    if ((s.ntail || tail_lds_always) && s.lds < 2 * CTF_MT_N * 4) s.lds = 2 * CTF_MT_N * 4;
+    return s;
+}
+extern "C" int ctf_step_blocks(const DevCfg& cfg) { return step_shape(cfg, step_lanes(cfg), cfg.log_metrics != 0, false, false).nstep; }
 // with_tail: the ring regeneration rides at the tail of this launch.  Nothing in the launch depends on how many went before it
 // (see tail_block), so a captured launch can be replayed.
-extern "C" hipError_t ctf_launch_step(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64,
-                                      uint8_t* done, uint32_t flags, int with_tail, hipStream_t st) {
+extern "C" hipError_t ctf_launch_step(const DevCfg& cfg, const DevPtrs& p, const StepArgs& a, int with_tail, hipStream_t st) {
     const int w = step_lanes(cfg);
-    const bool tail = with_tail && cfg.rng_refill_every;
-    if (cfg.log_metrics) launch_step_m<true>(w, cfg, p, actions, rw32, rw64, done, flags, tail, st);
-    else launch_step_m<false>(w, cfg, p, actions, rw32, rw64, done, flags, tail, st);
+    const StepShape s = step_shape(cfg, w, cfg.log_metrics != 0, with_tail && cfg.rng_refill_every, true);
+    with_step_variant(cfg.log_metrics != 0, w, [&](auto M, auto W) {
+        hipLaunchKernelGGL((k_step<M.value, W.value>), dim3(s.nstep + s.ntail), dim3(WAVE), s.lds, st, cfg, p, a.actions, a.rw32, a.rw64, a.done,
+                           a.flags, s.nstep);
+    });
     return hipGetLastError();
 }
-// ---- k_step_observe (the launch's shape: see the kernel)
-template <bool METRICS, int W>
-static void launch_step_observe_w(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64, uint8_t* done,
-                                  uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, uint32_t* sync,
-                                  uint64_t spin_ticks, hipStream_t st) {
-    constexpr int EPW = WAVE / W;
-    const int nstep = (cfg.n_envs + EPW - 1) / EPW;
-    const int ntail = cfg.rng_refill_every ? (2 * cfg.n_envs + STEP_TAIL_PAIRS - 1) / STEP_TAIL_PAIRS : 0;
-    const int tile0 = (nstep + ntail + 7) / 8 * 8;
-    const int ntiles = cfg.tile_nb * CTF_OBS_TILE_WPB;
-    size_t sh = (size_t)EPW * step_slot_bytes(cfg.GS, cfg.RS, cfg.N, METRICS);
-    if (ntail && sh < 2 * CTF_MT_N * 4) sh = 2 * CTF_MT_N * 4;
-    if (sh < (size_t)tiles_wave_bytes(cfg.RS, cfg.N, cfg.M)) sh = (size_t)tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
-    const char* xenv = getenv("CTF_OBS_XCD");  // 0: launch-order tiles (profiling); default: XCD-contiguous
-    const uint32_t xcd_map = xenv ? (atoi(xenv) != 0) : 1u;
-    const dim3 grid((unsigned)(tile0 + ntiles)), block(WAVE);
-    if (cfg.obs_store_nt)
-        hipLaunchKernelGGL((k_step_observe<METRICS, W, 1>), grid, block, sh, st, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask,
-                           xcd_map, sync, nstep, ntail, tile0, spin_ticks);
-    else
-        hipLaunchKernelGGL((k_step_observe<METRICS, W, 0>), grid, block, sh, st, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask,
-                           xcd_map, sync, nstep, ntail, tile0, spin_ticks);
-}
-template <bool METRICS>
-static void launch_step_observe_m(int w, const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64, uint8_t* done,
-                                  uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, uint32_t* sync, uint64_t spin_ticks,
-                                  hipStream_t st) {
-    if (w <= 1) launch_step_observe_w<METRICS, 1>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
-    else if (w == 2) launch_step_observe_w<METRICS, 2>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
-    else if (w == 4) launch_step_observe_w<METRICS, 4>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
-    else launch_step_observe_w<METRICS, 8>(cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
-}
-extern "C" int ctf_step_blocks(const DevCfg& cfg) { return (cfg.n_envs + WAVE / step_lanes(cfg) - 1) / (WAVE / step_lanes(cfg)); }
 #if STEP_TRACE
 // what the runtime thinks fits: blocks of k_step<true, 4> per CU at `lds` bytes of dynamic LDS, and the device's LDS per CU
 extern "C" int ctf_debug_step_occupancy(int lds, int* blocks_per_cu, int* lds_per_cu, int* lds_per_block) {
@@ -1594,39 +1235,42 @@ extern "C" int ctf_debug_step_occupancy(int lds, int* blocks_per_cu, int* lds_pe
     return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_step<true, 4>, WAVE, (size_t)lds);
 }
 #endif
-static int obs_reserve_blocks() {
-    static const int v = [] { const char* e = getenv("CTF_OBS_RESERVE_BLOCKS"); return e ? atoi(e) : 0; }();
-    return v < 0 ? 0 : v;
-}
 static int observe_align(const DevCfg& cfg, const uint8_t* obs) {
     const uintptr_t a = (uintptr_t)obs;
     return ((cfg.obs_bytes % 16) == 0 && (a % 16) == 0) ? 16 : (((cfg.obs_bytes % 4) == 0 && (a % 4) == 0) ? 4 : 1);
 }
-// the one rule by which a render into `obs` is the tile kernel (1) or the wave-per-env kernel (0)
+// the one rule by which a render into `obs` is the tile kernel (1) or the wave-per-env kernel (0); CTF_OBS_TILES = 0 / 1: never /
+// whenever possible (tests, profiling)
 extern "C" int ctf_observe_uses_tiles(const DevCfg& cfg, const uint8_t* obs) {
-    const char* tenv = getenv("CTF_OBS_TILES");  // 0 / 1: never / whenever possible (tests, profiling)
-    return obs && observe_align(cfg, obs) == 16 && cfg.tile_k > 0 && (tenv ? atoi(tenv) != 0 : OBS_TILES_DEFAULT);
+    return obs && observe_align(cfg, obs) == 16 && cfg.tile_k > 0 && env_int("CTF_OBS_TILES", OBS_TILES_DEFAULT) != 0;
 }
-// the one rule by which ctf_step_observe is one launch (1: k_step_observe) or two (0): where the tile render applies and it is asked for
+// the one rule by which ctf_step_observe is one launch (1: k_step_observe) or two (0): where the tile render applies and it is
+// asked for (CTF_STEP_OBSERVE_ONE_LAUNCH = 0 / 1: never / whenever possible)
 extern "C" int ctf_step_observe_one_launch(const DevCfg& cfg, const uint8_t* obs) {
-    const char* env = getenv("CTF_STEP_OBSERVE_ONE_LAUNCH");  // 0 / 1: never / whenever possible (tests, profiling)
-    return ctf_observe_uses_tiles(cfg, obs) && (env ? atoi(env) != 0 : STEP_OBSERVE_ONE_LAUNCH_DEFAULT);
+    return ctf_observe_uses_tiles(cfg, obs) && env_int("CTF_STEP_OBSERVE_ONE_LAUNCH", STEP_OBSERVE_ONE_LAUNCH_DEFAULT) != 0;
 }
-// sync: the handle's sync words (ctf_sync_words); spin_ticks: a tile's bound on its wait, in wall-clock ticks
-extern "C" hipError_t ctf_launch_step_observe(const DevCfg& cfg, const DevPtrs& p, const int8_t* actions, float* rw32, double* rw64,
-                                              uint8_t* done, uint32_t flags, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask,
-                                              uint32_t* sync, uint64_t spin_ticks, hipStream_t st) {
+// k_step_observe (the launch's shape: see the kernel)
+extern "C" hipError_t ctf_launch_step_observe(const DevCfg& cfg, const DevPtrs& p, const StepArgs& a, const RenderArgs& r, hipStream_t st) {
     const int w = step_lanes(cfg);
-    if (cfg.log_metrics) launch_step_observe_m<true>(w, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
-    else launch_step_observe_m<false>(w, cfg, p, actions, rw32, rw64, done, flags, obs, meta, reverse_mask, sync, spin_ticks, st);
+    const StepShape s = step_shape(cfg, w, cfg.log_metrics != 0, cfg.rng_refill_every != 0, false);
+    const int tile0 = (s.nstep + s.ntail + 7) / 8 * 8;
+    const int ntiles = cfg.tile_nb * CTF_OBS_TILE_WPB;
+    const size_t tile_lds = (size_t)tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
+    const size_t sh = s.lds < tile_lds ? tile_lds : s.lds;
+    const uint32_t xcd_map = obs_xcd_knob();
+    with_step_variant(cfg.log_metrics != 0, w, [&](auto M, auto W) {
+        with_bool(cfg.obs_store_nt != 0, [&](auto NT) {
+            hipLaunchKernelGGL((k_step_observe<M.value, W.value, NT.value>), dim3((unsigned)(tile0 + ntiles)), dim3(WAVE), sh, st, cfg, p, a.actions,
+                               a.rw32, a.rw64, a.done, a.flags, r.obs, r.meta, r.reverse_mask, xcd_map, r.sync, s.nstep, s.ntail, tile0,
+                               r.spin_ticks);
+        });
+    });
     return hipGetLastError();
 }
-extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask,
-                                         int n_cus, hipStream_t st) {
-    const int align = observe_align(cfg, obs);
-    const bool tiles = ctf_observe_uses_tiles(cfg, obs) != 0;
-    if (tiles) {
-        // one wave per tile, 4 independent waves per block; tile_bx blocks per group of tile_k envs (whose blocks fill tile_tpg tiles)
+extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, const RenderArgs& r, int n_cus, hipStream_t st) {
+    if (ctf_observe_uses_tiles(cfg, r.obs)) {
+        // one wave per tile, CTF_OBS_TILE_WPB independent waves per block; tile_bx blocks per group of tile_k envs (whose blocks fill
+        // tile_tpg tiles)
         const int wpb = CTF_OBS_TILE_WPB;
         size_t sh = (size_t)wpb * tiles_wave_bytes(cfg.RS, cfg.N, cfg.M);
         // At most 16 tile waves per CU, by the block's LDS (160 KiB per CU): fewer store streams in flight write the buffer
@@ -1634,46 +1278,42 @@ extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, ui
         // blocks without the cap and 0.2472 ms as the earlier blocks of 4 tiles; step + render 0.2790 / 0.2932 / 0.2980 ms
         // (profiles/r06_render_occupancy_cap.txt).
         if (sh < OBS_TILE_BLOCK_LDS) sh = OBS_TILE_BLOCK_LDS;
-        const char* xenv = getenv("CTF_OBS_XCD");  // 0: launch-order tiles (profiling); default: XCD-contiguous
-        const uint32_t xcd_map = xenv ? (atoi(xenv) != 0) : 1u;
-        if (cfg.obs_store_nt) hipLaunchKernelGGL(k_observe_tiles<1>, dim3((unsigned)cfg.tile_nb), dim3(wpb * WAVE), sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);
-        else hipLaunchKernelGGL(k_observe_tiles<0>, dim3((unsigned)cfg.tile_nb), dim3(wpb * WAVE), sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);
+        const uint32_t xcd_map = obs_xcd_knob();
+        with_bool(cfg.obs_store_nt != 0, [&](auto NT) {
+            hipLaunchKernelGGL(k_observe_tiles<NT.value>, dim3((unsigned)cfg.tile_nb), dim3(wpb * WAVE), sh, st, cfg, p, r.obs, r.meta, r.reverse_mask,
+                               xcd_map);
+        });
         return hipGetLastError();
     }
-    // waves per block: 4 unless one env's bitmap is so large that 4 of them would crowd the CU's LDS
     const int per_wave = obs_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes);
-    int wpb = 4;
-    while (wpb > 1 && wpb * per_wave > 40 * 1024) wpb >>= 1;
+    const int wpb = obs_waves_per_block(per_wave);
     const size_t sh = (size_t)wpb * per_wave;
     int blocks = (cfg.n_envs + wpb - 1) / wpb;
     // the CU's 32-wave limit, grid-stride beyond that; a few block slots stay free so that a concurrent small kernel
     // (the RCCL all-gather of the rollout tensors) can start beside this launch instead of behind it
     int cap = n_cus * (32 / wpb);
-    if (const char* ov = getenv("CTF_OBS_BLOCKS_PER_CU")) {  // profiling only: occupancy scaling of the render
-        const int v = atoi(ov);
-        if (v >= 1 && v < 32 / wpb) cap = n_cus * v;
-    }
+    const int per_cu = env_int("CTF_OBS_BLOCKS_PER_CU", 0);  // profiling only: occupancy scaling of the render
+    if (per_cu >= 1 && per_cu < 32 / wpb) cap = n_cus * per_cu;
     if (cap > 64) cap -= obs_reserve_blocks();
     if (blocks > cap) blocks = cap;
     const dim3 grid(blocks), block(wpb * WAVE);
-    const char* xenv = getenv("CTF_OBS_XCD");  // 0: plain grid-stride split of the envs (profiling)
-    const uint32_t xcd_map = (blocks % 8 == 0 && (xenv ? atoi(xenv) != 0 : true)) ? 1u : 0u;
-    if (align == 16) hipLaunchKernelGGL(k_observe<16>, grid, block, sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);
-    else if (align == 4) hipLaunchKernelGGL(k_observe<4>, grid, block, sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);
-    else hipLaunchKernelGGL(k_observe<1>, grid, block, sh, st, cfg, p, obs, meta, reverse_mask, xcd_map);
+    const uint32_t xcd_map = (blocks % 8 == 0 && obs_xcd_knob()) ? 1u : 0u;
+    const int align = observe_align(cfg, r.obs);
+    if (align == 16) hipLaunchKernelGGL(k_observe<16>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
+    else if (align == 4) hipLaunchKernelGGL(k_observe<4>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
+    else hipLaunchKernelGGL(k_observe<1>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
     return hipGetLastError();
 }
 extern "C" hipError_t ctf_launch_observe_codes(const DevCfg& cfg, const DevPtrs& p, uint8_t* codes, uint16_t* meta, uint16_t* selfcells,
                                                uint32_t reverse_mask, int n_cus, hipStream_t st) {
     const int per_wave = codes_wave_bytes(cfg.GS, cfg.RS, cfg.GG, cfg.N, cfg.M);
-    int wpb = 4;
-    while (wpb > 1 && wpb * per_wave > 40 * 1024) wpb >>= 1;
+    const int wpb = obs_waves_per_block(per_wave);
     const size_t sh = (size_t)wpb * per_wave;
     int blocks = (cfg.n_envs + wpb - 1) / wpb;
     if (blocks > n_cus * 8) blocks = n_cus * 8;
-    const bool dwords = ((cfg.N * cfg.GG) % 4) == 0 && ((uintptr_t)codes % 4) == 0;
-    if (dwords) hipLaunchKernelGGL(k_observe_codes<true>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, codes, meta, selfcells, reverse_mask);
-    else hipLaunchKernelGGL(k_observe_codes<false>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, codes, meta, selfcells, reverse_mask);
+    with_bool(((cfg.N * cfg.GG) % 4) == 0 && ((uintptr_t)codes % 4) == 0, [&](auto DWORDS) {
+        hipLaunchKernelGGL(k_observe_codes<DWORDS.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, codes, meta, selfcells, reverse_mask);
+    });
     return hipGetLastError();
 }
 extern "C" hipError_t ctf_launch_export_counters(const DevCfg& cfg, const DevPtrs& p, int32_t* metrics, int32_t* captures, int32_t* steps,
@@ -1682,29 +1322,6 @@ extern "C" hipError_t ctf_launch_export_counters(const DevCfg& cfg, const DevPtr
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_export_counters, dim3(blocks), dim3(256), 0, st, cfg, p, metrics, captures, steps);
-    return hipGetLastError();
-}
-// envs [e0, e0 + count): record b of the arrays belongs to env e0 + b
-extern "C" hipError_t ctf_launch_import_rng(const DevCfg& cfg, const DevPtrs& p, const uint32_t* py, const uint32_t* np_, int e0, int count,
-                                            hipStream_t st) {
-    hipLaunchKernelGGL(k_import_rng, dim3(count), dim3(256), 0, st, cfg, p, py, np_, e0);
-    return hipGetLastError();
-}
-extern "C" hipError_t ctf_launch_export_rng(const DevCfg& cfg, const DevPtrs& p, uint32_t* py, uint32_t* np_, int e0, int count, hipStream_t st) {
-    hipLaunchKernelGGL(k_export_rng, dim3(count), dim3(256), 0, st, cfg, p, py, np_, e0);
-    return hipGetLastError();
-}
-extern "C" hipError_t ctf_launch_rng_refill(const DevCfg& cfg, const DevPtrs& p, int e0, int count, int init, hipStream_t st) {
-    const int waves = (2 * count + RNG_PAIRS_PER_WAVE - 1) / RNG_PAIRS_PER_WAVE;
-    hipLaunchKernelGGL(k_rng_refill, dim3((waves + 3) / 4), dim3(256), 0, st, cfg, p, e0, count, init);
-    return hipGetLastError();
-}
-extern "C" hipError_t ctf_launch_get_counters(const DevCfg& cfg, const DevPtrs& p, unsigned long long* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_get_counters, dim3((cfg.n_envs + 63) / 64), dim3(64), 0, st, cfg, p, out);
-    return hipGetLastError();
-}
-extern "C" hipError_t ctf_launch_set_counters(const DevCfg& cfg, const DevPtrs& p, const unsigned long long* in, hipStream_t st) {
-    hipLaunchKernelGGL(k_set_counters, dim3((cfg.n_envs + 63) / 64), dim3(64), 0, st, cfg, p, in);
     return hipGetLastError();
 }
 extern "C" hipError_t ctf_launch_random_actions(const DevCfg& cfg, int8_t* actions, uint64_t seed, uint32_t step,

@@ -1,0 +1,55 @@
+// ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
+// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip and ctf_harvest.hip.  Every file that defines or calls one of these includes
+// this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ctf_device.h"
+#include "ctf_harvest.h"
+#include "ctf_snapshot.h"
+
+// what one step reads and writes (ctf_step's arguments)
+struct StepArgs {
+    const int8_t* actions;
+    float* rw32;
+    double* rw64;
+    uint8_t* done;
+    uint32_t flags;
+};
+// what one render writes (ctf_observe's arguments) ...
+struct RenderArgs {
+    uint8_t* obs;
+    uint16_t* meta;
+    uint32_t reverse_mask;
+    // ... and, for the one-launch form only: the handle's sync words (ctf_sync_words) and a tile's bound on its wait, in wall-clock ticks
+    uint32_t* sync;
+    uint64_t spin_ticks;
+};
+
+extern "C" {
+// ---- ctf_kernels.hip
+hipError_t ctf_launch_reset(const DevCfg&, const DevPtrs&, const uint8_t* mask, int init_perm, hipStream_t);
+hipError_t ctf_launch_step(const DevCfg&, const DevPtrs&, const StepArgs&, int with_tail, hipStream_t);
+hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, const StepArgs&, const RenderArgs&, hipStream_t);
+hipError_t ctf_launch_observe(const DevCfg&, const DevPtrs&, const RenderArgs&, int n_cus, hipStream_t);
+hipError_t ctf_launch_observe_codes(const DevCfg&, const DevPtrs&, uint8_t* codes, uint16_t* meta, uint16_t* selfcells, uint32_t reverse_mask,
+                                    int n_cus, hipStream_t);
+hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t* metrics, int32_t* captures, int32_t* steps, hipStream_t);
+hipError_t ctf_launch_random_actions(const DevCfg&, int8_t* actions, uint64_t seed, uint32_t step, uint32_t env_offset, hipStream_t);
+int ctf_step_blocks(const DevCfg&);                                // step blocks of a step launch
+int ctf_observe_uses_tiles(const DevCfg&, const uint8_t* obs);       // 1: a render into `obs` is k_observe_tiles, 0: k_observe
+int ctf_step_observe_one_launch(const DevCfg&, const uint8_t* obs);  // 1: ctf_step_observe is k_step_observe, 0: two launches
+// ---- ctf_rng.hip (envs [e0, e0 + count): record b of the arrays belongs to env e0 + b)
+hipError_t ctf_launch_seed(const DevCfg&, const DevPtrs&, const uint64_t* py_seeds, const uint64_t* np_seeds, hipStream_t);
+hipError_t ctf_launch_import_rng(const DevCfg&, const DevPtrs&, const uint32_t* py, const uint32_t* np_, int e0, int count, hipStream_t);
+hipError_t ctf_launch_export_rng(const DevCfg&, const DevPtrs&, uint32_t* py, uint32_t* np_, int e0, int count, hipStream_t);
+hipError_t ctf_launch_rng_refill(const DevCfg&, const DevPtrs&, int e0, int count, int init, hipStream_t);
+hipError_t ctf_launch_get_counters(const DevCfg&, const DevPtrs&, unsigned long long* out, hipStream_t);
+hipError_t ctf_launch_set_counters(const DevCfg&, const DevPtrs&, const unsigned long long* in, hipStream_t);
+// ---- ctf_snapshot.hip
+hipError_t ctf_launch_save_states(const SnapLayout&, const int32_t* idx, int n, uint8_t* dst, hipStream_t);
+hipError_t ctf_launch_load_states(const SnapLayout&, const uint8_t* src, const int32_t* idx, int n, hipStream_t);
+// ---- ctf_harvest.hip
+hipError_t ctf_launch_harvest(const HarvestArgs&, const int32_t* group, int n_groups, const uint8_t* mask, uint32_t flags, int64_t* out, hipStream_t);
+}

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctf_snapshot.h"
+#include "ctf_launch.h"
 
 #define SNAP_THREADS 256
 #define SNAP_LOG_SLOTS 32                           // vislog slots one wave moves for its 64 records

@@ -114,6 +114,21 @@ def test_every_step_lane_width(lanes, monkeypatch):
     a.close(), b.close()
 
 
+@pytest.mark.parametrize("lanes", [1, 2, 4, 8])
+@pytest.mark.parametrize("log_metrics,nt", [(False, None), (True, "1"), (False, "1")])
+def test_every_step_lane_width_of_the_other_variants(lanes, log_metrics, nt, monkeypatch):
+    """The rest of the one launch's dispatch: k_step_observe<METRICS, W, STORE_NT> without metrics and with hinted stores at every
+    W (the test above runs <true, W, 0>).  CTF_OBS_NT forces the hint at a size far below the rule's; 65 envs: at every width the
+    last step block is a ragged one of a single env."""
+    monkeypatch.setenv("CTF_STEP_W", str(lanes))  # both read when the handle is created
+    if nt is not None:
+        monkeypatch.setenv("CTF_OBS_NT", nt)
+    a, b = _twins("arena", 65, log_metrics=log_metrics)
+    assert a.observe_kernel() == "k_observe_tiles" and a.observe_stores() == ("nontemporal" if nt == "1" else "plain")
+    _run(a, b, 40, monkeypatch, f"W={lanes} metrics={log_metrics} nt={nt}", check_every=20)
+    a.close(), b.close()
+
+
 def test_captured_launch_replays(monkeypatch):
     """The launch reads no argument that moves from call to call: a captured graph of K one-launch steps replayed several times
     (the generation number in device memory advances by itself) equals the two-launch path called eagerly."""

@@ -213,19 +213,16 @@ def test_store_hint_follows_what_all_live_handles_on_the_device_write(monkeypatc
     a.close()
 
 
-@pytest.mark.parametrize("name", ["arena_stress", "split_random", "syn_edge_k1"])
-@pytest.mark.parametrize("lanes", [1, 2, 4, 8])
-def test_every_step_lane_width_matches_the_oracle(name, lanes, monkeypatch):
+def _lane_width_against_oracle(name, lanes, n_envs, steps, log_metrics, monkeypatch):
     """k_step gives every env a group of W lanes (W = the power of two covering the larger opponents list); CTF_STEP_W forces
     another width, with more tagging passes per turn (W < opponents) or idle lanes (W > opponents).  The slot -> lane rotation of
     the hit bits, the randint nibbles fetched from their owner lane and the split of the production all depend on W: every width
     must give the oracle's trajectory, MT19937 states included."""
     monkeypatch.setenv("CTF_STEP_W", str(lanes))
     case = Case(name)
-    n_envs, steps = 150, 140
     seeds = np.arange(n_envs, dtype=np.uint64) * 131 + 3
-    vec = pkg.VecGridworldCtf(n_envs, device=_dev(), py_seeds=seeds, np_seeds=seeds, **case.kwargs)
-    cfg, _ = case.config()
+    vec = pkg.VecGridworldCtf(n_envs, device=_dev(), py_seeds=seeds, np_seeds=seeds, log_metrics=log_metrics, **case.kwargs)
+    cfg, _ = case.config(log_metrics=log_metrics)
     refs = [oracle.OracleEnv(cfg) for _ in range(n_envs)]
     for e, r in enumerate(refs):
         r.seed(int(seeds[e]), int(seeds[e]))
@@ -255,6 +252,19 @@ def test_every_step_lane_width_matches_the_oracle(name, lanes, monkeypatch):
                     assert np.array_equal(py, rpy) and np.array_equal(npw, rnp), f"{name} W={lanes} env {e} step {t}: MT19937 states"
     assert alive.sum() >= (n_envs // 8 if name == "syn_edge_k1" else n_envs // 2)
     vec.close()
+
+
+@pytest.mark.parametrize("name", ["arena_stress", "split_random", "syn_edge_k1"])
+@pytest.mark.parametrize("lanes", [1, 2, 4, 8])
+def test_every_step_lane_width_matches_the_oracle(name, lanes, monkeypatch):
+    _lane_width_against_oracle(name, lanes, 150, 140, True, monkeypatch)
+
+
+@pytest.mark.parametrize("lanes", [1, 2, 4, 8])
+def test_every_step_lane_width_without_metrics_matches_the_oracle(lanes, monkeypatch):
+    """The other half of the step launch's dispatch: k_step<METRICS = false, W> at every W (the test above runs METRICS = true).
+    65 envs: no multiple of 64, 32, 16 or 8, so at every width the last step block is a ragged one of a single env."""
+    _lane_width_against_oracle("arena_stress", lanes, 65, 40, False, monkeypatch)
 
 
 def _run_against_oracle(vec, cfg, case, seeds, steps, ctx, np_seeds=None, counters=False):

@@ -40,7 +40,8 @@ for i, flags in enumerate(sys.argv[1:]):
             so = pre
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wl,-Bsymbolic",
                                "-I" + os.path.join(ROOT, "marl-ctf-development_amd", "csrc")]
-                              + flags_only.split() + ["-shared", "-o", so, os.path.join(src, "ctf_abi.hip"), os.path.join(src, "ctf_kernels.hip")])
+                              + flags_only.split() + ["-shared", "-o", so]
+                              + [os.path.join(src, f) for f in subprocess.check_output(["make", "-s", "-C", src, "print-srcs"], text=True).split()])
     if os.environ.get("AB_BUILD_ONLY"):
         continue
     os.environ.update(ENVS[full])  # variables that are read when the handle is created (CTF_STEP_W)

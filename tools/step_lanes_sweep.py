@@ -1,5 +1,5 @@
-"""k_step alone at every lane width (CTF_STEP_W) over a range of batch sizes: where does the automatic rule (ctf_kernels.hip:
-step_lanes) leave time on the table?  Usage: python tools/step_lanes_sweep.py [arena|split]"""
+"""k_step alone at every lane width (CTF_STEP_W) over a range of batch sizes: where does the automatic rule (step_lanes() in
+ctf_kernels.hip) leave time on the table?  Usage: python tools/step_lanes_sweep.py [arena|split]"""
 import importlib
 import os
 import sys

@@ -12,11 +12,14 @@ import numpy as np
 pkg = importlib.import_module("marl-ctf-development_amd")
 abi = pkg._abi
 CS = os.path.join(ROOT, "marl-ctf-development_amd", "csrc")
+def csrc_sources(d):
+    """The library's own source list (csrc/Makefile), as paths under d."""
+    return [os.path.join(d, f) for f in subprocess.check_output(["make", "-s", "-C", d, "print-srcs"], text=True).split()]
 so = os.path.join(ROOT, "tools", "_ab", "libtrace%s.so" % os.environ.get("TRACE_TAG", ""))
 if not os.path.exists(so) or os.environ.get("AB_BUILD_ONLY"):
     os.makedirs(os.path.dirname(so), exist_ok=True)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wl,-Bsymbolic",
-                           "-I" + CS, "-DSTEP_TRACE=1"] + sys.argv[1:] + ["-shared", "-o", so, os.path.join(CS, "ctf_abi.hip"), os.path.join(CS, "ctf_kernels.hip")])
+                           "-I" + CS, "-DSTEP_TRACE=1"] + sys.argv[1:] + ["-shared", "-o", so] + csrc_sources(CS))
 if os.environ.get("AB_BUILD_ONLY"):
     sys.exit(0)
 import torch

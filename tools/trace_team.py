@@ -17,8 +17,8 @@ so = os.path.join(ROOT, "tools", "_ab", "libctf_hip_trace.so")
 os.makedirs(os.path.dirname(so), exist_ok=True)
 if not os.path.exists(so):
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function",
-                           "-ffp-contract=off", "-DPOL_TRACE=1", "-shared", "-o", so] + [os.path.join(src, f) for f in
-                          ("ctf_abi.hip", "ctf_kernels.hip", "ctf_policy.hip")])
+                           "-ffp-contract=off", "-DPOL_TRACE=1", "-shared", "-o", so]
+                          + [os.path.join(src, f) for f in subprocess.check_output(["make", "-s", "-C", src, "print-srcs"], text=True).split()])
 if len(sys.argv) > 1 and sys.argv[1] == "build":
     sys.exit(0)
 os.environ["CTF_LIB_PATH"] = so
