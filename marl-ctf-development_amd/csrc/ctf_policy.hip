@@ -6,21 +6,9 @@
 //   k_policy_features_team   the same for agents that share a view: the convolutions once per env, a patch per agent
 //   k_policy_head            tanh, fc2, tanh, heads, mask, sample, log-prob, entropy (agent_network.py:37-40,63-81)
 //
-// k_policy_features — one wave per sample, everything between the code bytes and the activation row stays on the CU:
-//   h0  LDS bf16 [2 halves][G*G cells][8 ch]  the one-hot input, written straight from the codes (channel halves in separate
-//           arrays: a lane's 16-byte operand reads then fall on consecutive addresses across lanes — no bank conflicts)
-//   conv1 = 16x16x32 MFMAs: D[out ch][position] over K = (2 taps) x (16 in ch); A = weights, register-resident for the
-//           whole launch; B = ds_read_b128 of h0 rows (a lane's 8 consecutive channels of one cell)
-//   h1  LDS bf16 [2 halves][G1*G1 positions][8 ch]  tanh(conv1), written 8 bytes per lane from the accumulator layout
-//   conv2 = 32x32x16 MFMAs: D[out ch][position], one MFMA per tap (K = 16 in ch), B = ds_read_b128 of h1 rows
-//   out HBM bf16 [sample][Kp]            tanh(conv2) as 8-byte stores in the order the accumulators hold it:
-//           column ((c/4) * PP + p) * 4 + c%4 for out channel c, position p (PP = positions rounded up to whole
-//           32-position tiles, so that every store instruction covers whole 128-byte lines) — the fc1 weight's columns
-//           are permuted to this order once on the host (policy_native.py), so no transpose happens anywhere; then the M
-//           metadata values (f16 -> bf16) and padding up to Kp (a multiple of 64: rows are whole lines).
-// tanh(x) = 1 - 2 / (2^(x * 2 log2 e) + 1): the factor 2 log2 e is folded into the conv weights and biases on the host,
-// so a pair of activations costs 2 v_exp_f32, v_pk_add_f32, 2 v_rcp_f32, v_pk_fma_f32, v_cvt_pk_bf16_f32.
+// The front's layout (h0, conv1, h1, conv2, the activation row) is shared by the three forward kernels: ctf_policy_front_dev.h.
 // fc1 is a plain GEMM and stays with hipBLASLt (through torch).
+#include "ctf_policy_front_dev.h"
 #include "ctf_policy_host.h"
 
 // One LDS image of this wave ([2 channel halves][rows][8 channels] bf16) -> global memory channels-last ([rows][16 channels]): 16-byte
@@ -51,34 +39,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     uint8_t* h1 = h0 + pol_h0_bytes(G);
     const int H0A = GG * 16, H1A = pol_h1_bytes(G) / 2;  // bytes of one channel-half array
 
-    // ---- launch-lifetime registers: both convolutions' weights in MFMA A-operand order, and the biases
-    u32x4_t w1[5], w2[9];
-#pragma unroll
-    for (int s = 0; s < 5; s++) w1[s] = a.w1frag[s * WAVE + lane];
-#pragma unroll
-    for (int t = 0; t < 9; t++) w2[t] = a.w2frag[t * WAVE + lane];
-    f32x4_t bias1;
-#pragma unroll
-    for (int r = 0; r < 4; r++) bias1[r] = a.b1[(lane >> 4) * 4 + r];
-    f32x16_t bias2;
-#pragma unroll
-    for (int r = 0; r < 16; r++) bias2[r] = a.b2[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-
-    // conv1 B-operand geometry: lane = (position n = lane & 15, k-group g = lane >> 4): taps 2s + (g >> 1), channels 8 (g & 1) ..
-    const int n1 = lane & 15, g1 = lane >> 4;
-    int off1[5];
-#pragma unroll
-    for (int s = 0; s < 5; s++) {
-        const int tap = min(2 * s + (g1 >> 1), 8);  // "tap 9" has zero weights: any valid address
-        off1[s] = ((tap / 3) * G + (tap % 3)) * 16 + (g1 & 1) * H0A;
-    }
-    // position 16 t + n walks the G1 x G1 output row-major: per tile it advances 16 = dy1 rows + dx1 columns
-    const int y1_0 = (int)(((uint32_t)n1 * a.inv_g1) >> 16), x1_0 = n1 - y1_0 * G1;
-    const int dy1 = 16 / G1, dx1 = 16 - dy1 * G1;
-    // conv1 output: this lane's 4 channels 4 g .. 4 g + 3 of position n, as 8 bytes of half g >> 1
-    uint8_t* h1w = h1 + (g1 >> 1) * H1A + n1 * 16 + (g1 & 1) * 8;
-    // conv2: lane = (position n = lane & 31, channel half h = lane >> 5)
-    const int n2 = lane & 31, hh = lane >> 5;
+    PolFront f;
+    pol_front_prologue<TG>(f, a, h1);
 
     const int S = a.n_sel * a.n_envs;
     const int s_first = blockIdx.x * wpb + wave, s_stride = gridDim.x * wpb;
@@ -147,67 +109,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
                 *(u32x4_t*)(h0 + H0A + c * 16) = (u32x4_t){w[4], w[5], w[6], w[7]};
             }
         }
-        // metadata: f16 -> bf16 pairs behind the conv features; then ONE column of 1.0 (column 32 PP + M: a caller may keep fc1's bias
-        // in that column of its weight — the training path does, so that the bias gradient falls out of the weight-gradient GEMM; the
-        // inference weights hold zero there); zero padding to Kp
-        if (lane < npair) {
-            uint32_t out = lane == (a.M >> 1) ? 0x3F80u : 0u;
-            if (lane < (a.M >> 1)) {
-                const float lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(two & 0xFFFFu));
-                const float hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(two >> 16));
-                out = pack_bf16(lo, hi);
-            }
-            ((uint32_t*)(arow + 32 * PP))[lane] = out;
-        }
+        // metadata: f16 -> bf16 pairs behind the conv features, the column of 1.0, zero padding to Kp
+        if (lane < npair) ((uint32_t*)(arow + 32 * PP))[lane] = pol_meta_word(two, lane, a.M, true);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
         if (TRAIN && a.h0_out) pol_store_image(h0, H0A, GG, a.h0_out + (size_t)s * GG * 16, lane);
 
-        // ---- conv1 + tanh -> h1.  (Positions >= P1 of the last tile read past h0 into h1 — inside this wave's LDS — and
-        // land in h1 rows >= P1, which nothing reads.)
-        const int T1 = (P1 + 15) >> 4;
-        int x1 = x1_0, cell1 = y1_0 * G + x1_0;
-        // two tiles per pass: two independent accumulation chains keep the MFMA pipe and the LDS busy within one wave
-        int t = 0;
-#pragma unroll 1
-        for (; t + 1 < T1; t += 2) {
-            const uint8_t* base_a = h0 + ((POL_ABLATE & 8) ? 0 : cell1 * 16);
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            const uint8_t* base_b = h0 + ((POL_ABLATE & 8) ? 64 : cell1 * 16);
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            f32x4_t acc_a = bias1, acc_b = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                const u32x4_t bb = *(const u32x4_t*)(base_b + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(bb), acc_b, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;  // rows up to 16 * T1 exist
-            o[0] = tanh2_pack(acc_b[0], acc_b[1]);
-            o[1] = tanh2_pack(acc_b[2], acc_b[3]);
-            *(u32x2_t*)(h1w + 16 * (t + 1) * 16) = o;
-        }
-        if (t < T1) {  // odd tile count: the last one alone
-            const uint8_t* base_a = h0 + ((POL_ABLATE & 8) ? 0 : cell1 * 16);
-            f32x4_t acc_a = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;
-        }
+        // ---- conv1 + tanh -> h1
+        pol_conv1_pass(f, h0, G, (P1 + 15) >> 4);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
         if (TRAIN) pol_store_image(h1, H1A, P1, a.h1_out + (size_t)s * P1 * 16, lane);
@@ -216,40 +125,32 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
         const int T2 = (P2 + 31) >> 5;
 #pragma unroll 1
         for (int t = 0; t < T2; t += 2) {
-            const int pa = 32 * t + n2, pb = pa + 32;
+            // (pol_conv2_pair's arithmetic in this kernel's own text: it stores tile by tile and guards the second tile, and through
+            // the helper's quad-by-quad store functor the compiler schedules the G = 11 and runtime-G instantiations differently)
+            const int pa = 32 * t + f.n2, pb = pa + 32;
             const int pca = min(pa, P2 - 1), pcb = min(pb, P2 - 1);
             const int ya = (int)(((uint32_t)pca * a.inv_g2) >> 16), yb = (int)(((uint32_t)pcb * a.inv_g2) >> 16);
-            const uint8_t* base_a = h1 + ((POL_ABLATE & 8) ? 0 : (ya * G1 + (pca - ya * G2)) * 16 + hh * H1A);
-            const uint8_t* base_b = h1 + ((POL_ABLATE & 8) ? 64 : (yb * G1 + (pcb - yb * G2)) * 16 + hh * H1A);
-            f32x16_t acc_a = bias2, acc_b = bias2;
+            const uint8_t* base_a = h1 + ((POL_ABLATE & 8) ? 0 : (ya * G1 + (pca - ya * G2)) * 16 + f.hh * H1A);
+            const uint8_t* base_b = h1 + ((POL_ABLATE & 8) ? 64 : (yb * G1 + (pcb - yb * G2)) * 16 + f.hh * H1A);
+            f32x16_t acc_a = f.bias2, acc_b = f.bias2;
 #pragma unroll
             for (int tap = 0; tap < 9; tap++) {
                 const int off = ((tap / 3) * G1 + (tap % 3)) * 16;
                 const u32x4_t ba = *(const u32x4_t*)(base_a + off);
                 const u32x4_t bb = *(const u32x4_t*)(base_b + off);
-                acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(bb), acc_b, 0, 0, 0);
+                acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(f.w2[tap]), as_bf16x8(ba), acc_a, 0, 0, 0);
+                acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(f.w2[tap]), as_bf16x8(bb), acc_b, 0, 0, 0);
             }
             // one address per pass: the four channel groups of a lane sit (2 q - 3) * P2 * 4 elements around `mid`
-            uint16_t* mid = arow + ((3 + hh) * PP + pa) * 4;
+            uint16_t* mid = arow + ((3 + f.hh) * PP + pa) * 4;
             // every lane stores, also the positions past P2 of the last tile (finite values under zero fc1 weights): whole lines
             if ((POL_ABLATE & 1) ? (acc_a[0] == 12345.0f && acc_b[5] == 1.0f) : true) {
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    u32x2_t o;
-                    o[0] = tanh2_pack(acc_a[4 * q], acc_a[4 * q + 1]);
-                    o[1] = tanh2_pack(acc_a[4 * q + 2], acc_a[4 * q + 3]);
-                    *(u32x2_t*)(mid + (2 * q - 3) * PP * 4) = o;
-                }
+                for (int q = 0; q < 4; q++) *(u32x2_t*)(mid + (2 * q - 3) * PP * 4) = pol_tanh4(acc_a, q);
             }
             if ((POL_ABLATE & 1) ? (acc_b[0] == 12345.0f && acc_a[7] == 1.0f) : (pb < PP)) {
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    u32x2_t o;
-                    o[0] = tanh2_pack(acc_b[4 * q], acc_b[4 * q + 1]);
-                    o[1] = tanh2_pack(acc_b[4 * q + 2], acc_b[4 * q + 3]);
-                    *(u32x2_t*)(mid + (2 * q - 3) * PP * 4 + 32 * 4) = o;
-                }
+                for (int q = 0; q < 4; q++) *(u32x2_t*)(mid + (2 * q - 3) * PP * 4 + 32 * 4) = pol_tanh4(acc_b, q);
             }
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -323,33 +224,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     constexpr int H0A = GG * 16;
     const int H1A = pol_h1_bytes(G) / 2;
 
-    u32x4_t w1[5], w2[9];
-#pragma unroll
-    for (int s = 0; s < 5; s++) w1[s] = a.w1frag[s * WAVE + lane];
-#pragma unroll
-    for (int t = 0; t < 9; t++) w2[t] = a.w2frag[t * WAVE + lane];
-    f32x4_t bias1;
-#pragma unroll
-    for (int r = 0; r < 4; r++) bias1[r] = a.b1[(lane >> 4) * 4 + r];
-    f32x16_t bias2;
-#pragma unroll
-    for (int r = 0; r < 16; r++) bias2[r] = a.b2[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-
-    const int n1 = lane & 15, g1 = lane >> 4;
-    int off1[5];
-#pragma unroll
-    for (int s = 0; s < 5; s++) {
-        const int tap = min(2 * s + (g1 >> 1), 8);
-        off1[s] = ((tap / 3) * G + (tap % 3)) * 16 + (g1 & 1) * H0A;
-    }
-    const int y1_0 = (int)(((uint32_t)n1 * a.inv_g1) >> 16), x1_0 = n1 - y1_0 * G1;
-    constexpr int dy1 = 16 / G1, dx1 = 16 - dy1 * G1;
-    uint8_t* h1w = h1 + (g1 >> 1) * H1A + n1 * 16 + (g1 & 1) * 8;
-    const int n2 = lane & 31, hh = lane >> 5;
+    PolFront f;
+    pol_front_prologue<TG>(f, a, h1);
     // patch tiles: conv1 lane n -> offset (n / 3, n % 3) of the 3 x 3 patch (n < 9), conv2 lane n -> (n / 5, n % 5) (n < 25)
-    const int j1 = min(n1, 8), pdy1 = j1 / 3, pdx1 = j1 - 3 * pdy1;
-    const int j2 = min(n2, 24), pdy2 = j2 / 5, pdx2 = j2 - 5 * pdy2;
-    const int h1w_half = (g1 >> 1) * H1A + (g1 & 1) * 8;
+    const int j1 = min(f.n1, 8), pdy1 = j1 / 3, pdx1 = j1 - 3 * pdy1;
+    const int j2 = min(f.n2, 24), pdy2 = j2 / 5, pdx2 = j2 - 5 * pdy2;
+    const int h1w_half = (f.g1 >> 1) * H1A + (f.g1 & 1) * 8;
 
     const int npair = (a.Kp - 32 * PP) >> 1;
     const int e_first = blockIdx.x * wpb + wave, e_stride = gridDim.x * wpb;
@@ -398,48 +278,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
 
         // ---- shared conv1 + tanh -> h1, two tiles in flight (the launch runs one wave per SIMD — see the launcher — so
         // registers are plentiful and the wave's own instruction-level parallelism is all there is)
-        constexpr int T1 = (P1 + 15) >> 4;
-        int x1 = x1_0, cell1 = y1_0 * G + x1_0;
-        int t = 0;
-#pragma unroll 1
-        for (; t + 1 < T1; t += 2) {
-            const uint8_t* base_a = h0 + cell1 * 16;
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            const uint8_t* base_b = h0 + cell1 * 16;
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            f32x4_t acc_a = bias1, acc_b = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                const u32x4_t bb = *(const u32x4_t*)(base_b + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(bb), acc_b, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;
-            o[0] = tanh2_pack(acc_b[0], acc_b[1]);
-            o[1] = tanh2_pack(acc_b[2], acc_b[3]);
-            *(u32x2_t*)(h1w + 16 * (t + 1) * 16) = o;
-        }
-        if (t < T1) {
-            const uint8_t* base_a = h0 + cell1 * 16;
-            f32x4_t acc_a = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;
-        }
+        pol_conv1_pass(f, h0, G, (P1 + 15) >> 4);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
         POL_STAMP(2);
@@ -450,29 +289,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         static_assert((T2 & 1) == 0, "tile pairs");
 #pragma unroll 1
         for (int t2 = 0; t2 < T2; t2 += 2) {
-            const int pa = 32 * t2 + n2, pb = pa + 32;
-            const int pca = min(pa, P2 - 1), pcb = min(pb, P2 - 1);
-            const int ya = (int)(((uint32_t)pca * a.inv_g2) >> 16), yb = (int)(((uint32_t)pcb * a.inv_g2) >> 16);
-            const uint8_t* base_a = h1 + (ya * G1 + (pca - ya * G2)) * 16 + hh * H1A;
-            const uint8_t* base_b = h1 + (yb * G1 + (pcb - yb * G2)) * 16 + hh * H1A;
-            f32x16_t acc_a = bias2, acc_b = bias2;
-#pragma unroll
-            for (int tap = 0; tap < 9; tap++) {
-                const int off = ((tap / 3) * G1 + (tap % 3)) * 16;
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off);
-                const u32x4_t bb = *(const u32x4_t*)(base_b + off);
-                acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(bb), acc_b, 0, 0, 0);
-            }
             // every lane stores (also the positions past P2 of the last tile: finite values under zero fc1 weights): whole lines
-            const uint32_t lane_off = (uint32_t)(((3 + hh) * PP + pa) * 8);  // the four channel groups sit (2 q - 3) * PP * 8 around it
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                u32x2_t oa, ob;
-                oa[0] = tanh2_pack(acc_a[4 * q], acc_a[4 * q + 1]);
-                oa[1] = tanh2_pack(acc_a[4 * q + 2], acc_a[4 * q + 3]);
-                ob[0] = tanh2_pack(acc_b[4 * q], acc_b[4 * q + 1]);
-                ob[1] = tanh2_pack(acc_b[4 * q + 2], acc_b[4 * q + 3]);
+            const uint32_t lane_off = (uint32_t)(((3 + f.hh) * PP + 32 * t2 + f.n2) * 8);  // the four channel groups sit (2 q - 3) * PP * 8 around it
+            pol_conv2_pair(f, h1, H1A, G, a.inv_g2, t2, [&](int q, u32x2_t oa, u32x2_t ob) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     if (k < A && !((POL_ABLATE & 32) && (q & 1))) {
@@ -480,7 +299,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                         *(u32x2_t*)(act_env + k * agent_stride + lane_off + (2 * q - 3) * PP * 8 + 256) = ob;
                     }
                 }
-            }
+            });
         }
         POL_STAMP(3);
         // the patch stores below hit addresses written above: have those writes acknowledged first.  The same drain is the
@@ -501,36 +320,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             const uint32_t mw = k == 0 ? metaw[0] : k == 1 ? metaw[1] : k == 2 ? metaw[2] : metaw[3];
             const int syk = sc / G, sxk = sc - syk * G;
             uint8_t* const arow = act_env + k * agent_stride;
-            if (lane < npair) {  // metadata behind the conv features, then the column of 1.0 (see k_policy_features)
-                uint32_t out = lane == (a.M >> 1) ? 0x3F80u : 0u;
-                if (lane < (a.M >> 1)) {
-                    const float lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(mw & 0xFFFFu));
-                    const float hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(mw >> 16));
-                    out = pack_bf16(lo, hi);
-                }
-                ((uint32_t*)(arow + 32 * PP * 2))[lane] = out;
-            }
+            // metadata behind the conv features, then the column of 1.0
+            if (lane < npair) ((uint32_t*)(arow + 32 * PP * 2))[lane] = pol_meta_word(mw, lane, a.M, true);
             uint16_t* selfp = (uint16_t*)(h0 + sc * 16);  // channel 0 of the own cell
             if (lane == 0) *selfp = 0x3F80;
             // conv1 patch: outputs (sy - 2 + dy, sx - 2 + dx), dy, dx in 0..2
             const int oy1 = syk - 2 + pdy1, ox1 = sxk - 2 + pdx1;
-            const bool ok1 = n1 < 9 && (unsigned)oy1 < (unsigned)G1 && (unsigned)ox1 < (unsigned)G1;
+            const bool ok1 = f.n1 < 9 && (unsigned)oy1 < (unsigned)G1 && (unsigned)ox1 < (unsigned)G1;
             const int cy1 = min(max(oy1, 0), G1 - 1), cx1 = min(max(ox1, 0), G1 - 1);
             u32x2_t* h1p = (u32x2_t*)(h1 + h1w_half + (cy1 * G1 + cx1) * 16);
             const u32x2_t keep = *h1p;
             __builtin_amdgcn_s_waitcnt(0xC07F);
             __builtin_amdgcn_wave_barrier();
             {
-                const uint8_t* base = h0 + (cy1 * G + cx1) * 16;
-                f32x4_t acc = bias1;
-#pragma unroll
-                for (int q = 0; q < 5; q++) {
-                    const u32x4_t b = *(const u32x4_t*)(base + off1[q]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(b), acc, 0, 0, 0);
-                }
-                u32x2_t o;
-                o[0] = tanh2_pack(acc[0], acc[1]);
-                o[1] = tanh2_pack(acc[2], acc[3]);
+                const u32x2_t o = pol_tanh4(pol_conv1_tile(f, h0 + (cy1 * G + cx1) * 16));
                 if (ok1) *h1p = o;
             }
             __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -538,24 +341,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             // conv2 patch: outputs (sy - 4 + dy, sx - 4 + dx), dy, dx in 0..4
             {
                 const int oy2 = syk - 4 + pdy2, ox2 = sxk - 4 + pdx2;
-                const bool ok2 = n2 < 25 && (unsigned)oy2 < (unsigned)G2 && (unsigned)ox2 < (unsigned)G2;
+                const bool ok2 = f.n2 < 25 && (unsigned)oy2 < (unsigned)G2 && (unsigned)ox2 < (unsigned)G2;
                 const int cy2 = min(max(oy2, 0), G2 - 1), cx2 = min(max(ox2, 0), G2 - 1);
-                const uint8_t* base = h1 + (cy2 * G1 + cx2) * 16 + hh * H1A;
-                f32x16_t acc = bias2;
-#pragma unroll
-                for (int tap = 0; tap < 9; tap++) {
-                    const u32x4_t b = *(const u32x4_t*)(base + ((tap / 3) * G1 + (tap % 3)) * 16);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(b), acc, 0, 0, 0);
-                }
+                const f32x16_t acc = pol_conv2_tile(f, h1 + (cy2 * G1 + cx2) * 16 + f.hh * H1A, G1);
                 if (ok2) {
-                    const uint32_t lane_off = (uint32_t)(((3 + hh) * PP + oy2 * G2 + ox2) * 8);
+                    const uint32_t lane_off = (uint32_t)(((3 + f.hh) * PP + oy2 * G2 + ox2) * 8);
 #pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        u32x2_t o;
-                        o[0] = tanh2_pack(acc[4 * q], acc[4 * q + 1]);
-                        o[1] = tanh2_pack(acc[4 * q + 2], acc[4 * q + 3]);
-                        *(u32x2_t*)(arow + lane_off + (2 * q - 3) * PP * 8) = o;
-                    }
+                    for (int q = 0; q < 4; q++) *(u32x2_t*)(arow + lane_off + (2 * q - 3) * PP * 8) = pol_tanh4(acc, q);
                 }
             }
             // restore the shared image (the reads above are done: LDS serves a wave's operations in order)
@@ -693,15 +485,12 @@ extern "C" int ctf_policy_features(const uint8_t* codes_dev, const uint16_t* met
     if (meta_len < 2 || (meta_len & 1)) return ctf_policy_fail("meta_len must be even (2N + 6)");
     if (((uintptr_t)act_dev & 15) || ((uintptr_t)meta_dev & 3)) return ctf_policy_fail("act_dev must be 16-byte, meta_dev 4-byte aligned");
     if ((int64_t)n_envs * n_sel > 0x7FFFFFFF) return ctf_policy_fail("too many samples for one launch");
-    PolicyArgs a;
-    a.codes = codes_dev; a.meta = meta_dev; a.act = act_dev;
-    a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
-    a.w2frag = (const u32x4_t*)conv2_frag_dev; a.b2 = conv2_bias_dev;
-    a.n_envs = n_envs; a.N = n_agents; a.G = grid_size; a.M = meta_len; a.n_sel = n_sel;
-    a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    a.h0_out = nullptr; a.h1_out = nullptr;
-    if (pol_pack_sel(agent_sel, n_sel, n_agents, 16, &a.sel_pack)) return -1;
-    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
+    uint64_t sel_pack;
+    uint32_t inv_g1, inv_g2;
+    if (pol_pack_sel(agent_sel, n_sel, n_agents, 16, &sel_pack)) return -1;
+    if (pol_recips(grid_size, &inv_g1, &inv_g2)) return -1;
+    const PolicyArgs a = pol_front_args(codes_dev, meta_dev, act_dev, conv1_frag_dev, conv1_bias_dev, conv2_frag_dev, conv2_bias_dev, n_envs, n_agents,
+                                        grid_size, meta_len, n_sel, sel_pack, ctf_policy_act_stride(grid_size, meta_len), inv_g1, inv_g2, nullptr, nullptr);
 
     const int n_cus = ctf_policy_cus(device_id);
     if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
@@ -712,13 +501,7 @@ extern "C" int ctf_policy_features(const uint8_t* codes_dev, const uint16_t* met
     while (wpb > 1 && wpb * per_wave > 64 * 1024) wpb >>= 1;
     wpb = pol_env_int("CTF_POLICY_WPB", 1, wpb, wpb);  // profiling only
     const size_t sh = (size_t)wpb * per_wave;
-    int per_cu = (int)((160 * 1024) / sh);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu * wpb > 12) per_cu = 12 / wpb;  // 3 waves per SIMD: what the register budget allows
-    per_cu = pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, per_cu, per_cu);  // profiling only: occupancy scaling
-    const int S = n_envs * n_sel;
-    int blocks = (S + wpb - 1) / wpb;
-    if (blocks > n_cus * per_cu) blocks = n_cus * per_cu;
+    const int reg_cap = 12 / wpb;  // 3 waves per SIMD: what the register budget allows
     hipStream_t st = (hipStream_t)stream;
     if (shared_view_selfcell_dev && n_sel <= 4 && (grid_size == 15 || grid_size == 11)) {
         // agents sharing a view: one wave per env does the shared work once and a small patch per agent
@@ -729,26 +512,16 @@ extern "C" int ctf_policy_features(const uint8_t* codes_dev, const uint16_t* met
         // ONE block per CU, one wave per SIMD: measured 1.12 ms for the two teams of an arena step against 1.32 / 1.36 with two /
         // three blocks — every wave of this kernel keeps A activation rows open at once, and the more such streams a CU runs
         // the worse its store path does (the per-agent kernel, one row per wave, is the other way round: 1.80 / 1.57 / 1.51)
-        int team_per_cu = pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, 0x7FFFFFFF, 1);  // profiling only
-        if (team_per_cu > per_cu) team_per_cu = per_cu;
-        int tblocks = (n_envs + wpb - 1) / wpb;
-        if (tblocks > n_cus * team_per_cu) tblocks = n_cus * team_per_cu;
-        return pol_finish(pol_launch(grid_size == 15 ? k_policy_features_team<15> : k_policy_features_team<11>, tblocks, wpb * WAVE, sh, st, ta));
+        const int team_cap = min(pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, 0x7FFFFFFF, 1), reg_cap);  // profiling only
+        return pol_finish(pol_launch(grid_size == 15 ? k_policy_features_team<15> : k_policy_features_team<11>, pol_blocks(n_envs, wpb, sh, n_cus, team_cap),
+                                     wpb * WAVE, sh, st, ta));
     }
     void (*kernel)(PolicyArgs) = k_policy_features<15>;
     if (grid_size != 15) kernel = grid_size == 11 ? k_policy_features<11> : k_policy_features<0>;
-    return pol_finish(pol_launch(kernel, blocks, wpb * WAVE, sh, st, a));
+    const int per_cu_cap = pol_env_int("CTF_POLICY_BLOCKS_PER_CU", 1, reg_cap, reg_cap);  // profiling only: occupancy scaling
+    return pol_finish(pol_launch(kernel, pol_blocks((int64_t)n_envs * n_sel, wpb, sh, n_cus, per_cu_cap), wpb * WAVE, sh, st, a));
 }
 
-typedef short i16x4_t __attribute__((ext_vector_type(4)));
-// two transposed 4-position blocks (4 positions apart) -> one 8-position MFMA operand of this lane's channel
-__device__ __forceinline__ u32x4_t wgrad_tr_operand(const uint8_t* lds_addr, int second_block_bytes) {
-    typedef __attribute__((address_space(3))) i16x4_t* lds_v4;
-    const i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_addr));
-    const i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4)(lds_addr + second_block_bytes));
-    const u32x2_t l2 = __builtin_bit_cast(u32x2_t, lo), h2 = __builtin_bit_cast(u32x2_t, hi);
-    return (u32x4_t){l2[0], l2[1], h2[0], h2[1]};
-}
 // ---- tanh' * incoming gradient for two bf16 pairs (and their float32 values, for the bias-gradient sums)
 __device__ __forceinline__ uint32_t tanh_grad2(uint32_t g2, uint32_t h2, float& s0, float& s1) {  // two bf16 pairs -> g * (1 - h * h)
     const float g0 = __builtin_bit_cast(float, g2 << 16), g1 = __builtin_bit_cast(float, g2 & 0xFFFF0000u);
@@ -934,25 +707,14 @@ __global__ void __launch_bounds__(256) k_policy_front_dgrad(DgradArgs a) {
             }
             dgrad_tile_out(acc_a, pa_, ya_, xa_);
         }
-        if (W2) {
+        if constexpr (W2) {
             // ---- conv2's weight gradient: dW2[o][i][tap] += sum over positions of dz2[o][y][x] * h1[i][y + dy][x + dx].  K-step ks = gradient
             // rows 2 ks, 2 ks + 1; lane 4 q + p of a 16-lane group supplies block row q (position x0 + q) and channels 4 p .. 4 p + 3:
             // octet (p >> 1) + 2 h of dz2 / half p >> 1 of h1, 8 bytes in.  (All 64 lanes are active, as the transposing read requires.)
             const int kg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
             const int za = (tp >> 1) * ZCELLS * 16 + (((kg >> 1) + 2) * ZW + 8 * (kg & 1) + tq + 2) * 16 + (tp & 1) * 8;
             const int hb = (tp >> 1) * H1A + ((kg >> 1) * H1W + 8 * (kg & 1) + tq) * 16 + (tp & 1) * 8;
-#pragma unroll 1
-            for (int ks = 0; ks < KS; ks++) {
-                u32x4_t av[2];
-#pragma unroll
-                for (int h = 0; h < 2; h++) av[h] = wgrad_tr_operand(zp + za + h * 2 * ZCELLS * 16 + ks * 2 * ZW * 16, 4 * 16);
-#pragma unroll
-                for (int t = 0; t < 9; t++) {
-                    const u32x4_t bv = wgrad_tr_operand(h1 + hb + ((ks * 2 + t / 3) * H1W + t % 3) * 16, 4 * 16);
-#pragma unroll
-                    for (int h = 0; h < 2; h++) acc2[t][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(av[h]), as_bf16x8(bv), acc2[t][h], 0, 0, 0);
-                }
-            }
+            pol_wgrad_contract<2>(acc2, KS, zp + za, 2 * ZCELLS * 16, ZW * 16, 16, h1 + hb, H1W * 16, 16);
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();  // the next sample rewrites both images
@@ -987,24 +749,7 @@ __global__ void __launch_bounds__(256) k_policy_front_dgrad(DgradArgs a) {
             else atomicAdd(a.db1 + c, t);
         }
     }
-    if (W2) {  // the block's four partial weight gradients -> one; D tile: lane holds rows m = 4 (lane >> 4) + r of column n = lane & 15
-        __syncthreads();
-        const int mn = lane & 15, kg = lane >> 4;
-#pragma unroll
-        for (int t = 0; t < 9; t++)
-#pragma unroll
-            for (int h = 0; h < 2; h++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) red[((wave * 9 + t) * 32 + 16 * h + 4 * kg + r) * 16 + mn] = acc2[W2 ? t : 0][h][r];
-        __syncthreads();
-        for (int e = threadIdx.x; e < 9 * 32 * 16; e += blockDim.x) {
-            float v = 0.0f;
-            for (int w = 0; w < wpb; w++) v += red[w * 9 * 32 * 16 + e];
-            const int t = e / (32 * 16), oi = e - t * (32 * 16);
-            if (a.part) a.part[(size_t)blockIdx.x * DGRAD_PART + (size_t)oi * 9 + t] = v;
-            else atomicAdd(a.dw2 + (size_t)oi * 9 + t, v);  // [out][in][tap]
-        }
-    }
+    if constexpr (W2) pol_wgrad_reduce<2>(acc2, red, wave, wpb, lane, a.dw2, a.part, DGRAD_PART);  // the block's four partial weight gradients -> one
 }
 
 // deterministic mode: the blocks' slices of a.part -> the gradients k_policy_front_dgrad was asked for, in block order
@@ -1021,26 +766,21 @@ extern "C" int ctf_policy_front_dgrad(const uint16_t* d_act_dev, const uint16_t*
                                       int64_t n_samples, int32_t grid_size, int32_t meta_len, uint16_t* dz2_dev, uint16_t* dz1_dev,
                                       float* bias2_grad_dev, float* bias1_grad_dev, int32_t device_id, void* stream) {
     if (!d_act_dev || !act_dev || !h1_dev || !conv2_t_frag_dev || !dz2_dev || !dz1_dev) return ctf_policy_fail("null argument");
-    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (pol_train_check(grid_size, n_samples, 0, INT64_MAX)) return -1;
     if (((uintptr_t)d_act_dev | (uintptr_t)act_dev | (uintptr_t)dz2_dev | (uintptr_t)dz1_dev) & 7) return ctf_policy_fail("8-byte alignment");
     if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev) & 15) return ctf_policy_fail("h1_dev / conv2_t_frag_dev must be 16-byte aligned");
     if (!n_samples) return 0;
+    PolTrainSetup t;
+    if (pol_train_setup(grid_size, device_id, &t)) return -1;
     DgradArgs a;
     a.d_act = d_act_dev; a.act = act_dev; a.h1 = h1_dev; a.w2t = (const u32x4_t*)conv2_t_frag_dev; a.dz2 = dz2_dev; a.dz1 = dz1_dev;
     a.db2 = bias2_grad_dev; a.db1 = bias1_grad_dev; a.dw2 = nullptr; a.S = n_samples; a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
-    const int n_cus = ctf_policy_cus(device_id);
-    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    a.inv_g1 = t.inv_g1; a.inv_g2 = t.inv_g2;
     DeviceScope scope(device_id);
     if (scope.error) return ctf_policy_fail(scope.error);
     const int wpb = 4;
     const size_t sh = pol_dgrad_block_bytes(grid_size, false, wpb);
-    int per_cu = (int)((160 * 1024) / sh);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 2) per_cu = 2;
-    int64_t blocks = (n_samples + wpb - 1) / wpb;
-    if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
+    const int64_t blocks = pol_blocks(n_samples, wpb, sh, t.n_cus, 2);
     hipStream_t st = (hipStream_t)stream;
     const DetWorkspace det = ctf_policy_det(device_id);
     a.part = (det.ptr && (a.db2 || a.db1)) ? det.ptr : nullptr;
@@ -1100,7 +840,7 @@ __global__ void __launch_bounds__(128) k_policy_front_wgrad(WgradArgs a) {
     for (int t = 0; t < 9; t++)
 #pragma unroll
         for (int h = 0; h < NH; h++) acc[t][h] = (f32x4_t){0.0f, 0.0f, 0.0f, 0.0f};
-    const int mn = lane & 15, kg = lane >> 4;           // operand row / column, k-group: row parity kg >> 1, columns 8 (kg & 1) ..
+    const int kg = lane >> 4;                           // k-group: row parity kg >> 1, columns 8 (kg & 1) ..
     // the transposing read: lane 4 q + p of a 16-lane group supplies the address of block row q (position x0 + q), channels 4 p .. 4 p + 3
     const int tq = (lane & 15) >> 2, tp = lane & 3;
     const int a_off = (kg >> 1) * A_ROW + (8 * (kg & 1) + tq) * A_POS + tp * 8;   // + h * 32 bytes, + ks * 2 * A_ROW
@@ -1169,40 +909,13 @@ __global__ void __launch_bounds__(128) k_policy_front_wgrad(WgradArgs a) {
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
-        // ---- contraction: K-step ks = gradient rows 2 ks, 2 ks + 1; tap (dy, dx) reads the activation rows + dy from column + dx on.
-        // (All 64 lanes are active here, as the transposing read requires.)
-#pragma unroll 1
-        for (int ks = 0; ks < KS; ks++) {
-            u32x4_t av[NH];
-#pragma unroll
-            for (int h = 0; h < NH; h++) av[h] = wgrad_tr_operand(A + a_off + h * 32 + ks * 2 * A_ROW, 4 * A_POS);
-#pragma unroll
-            for (int t = 0; t < 9; t++) {
-                const u32x4_t bv = wgrad_tr_operand(B + b_off + (ks * 2 + t / 3) * B_ROW + (t % 3) * B_POS, 4 * B_POS);
-#pragma unroll
-                for (int h = 0; h < NH; h++) acc[t][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(av[h]), as_bf16x8(bv), acc[t][h], 0, 0, 0);
-            }
-        }
+        // ---- contraction (all 64 lanes are active here, as the transposing read requires)
+        pol_wgrad_contract<NH>(acc, KS, A + a_off, 32, A_ROW, A_POS, B + b_off, B_ROW, B_POS);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();  // the next sample rewrites both images
     }
-    // ---- the block's partial sums -> one; D tile: lane holds rows m = 4 (lane >> 4) + r of column n = lane & 15
-    __syncthreads();
-    float* red = (float*)lds;  // [wave][tap][CO][16]
-#pragma unroll
-    for (int t = 0; t < 9; t++)
-#pragma unroll
-        for (int h = 0; h < NH; h++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) red[((wave * 9 + t) * CO + 16 * h + 4 * kg + r) * 16 + mn] = acc[t][h][r];
-    __syncthreads();
-    for (int e = threadIdx.x; e < 9 * CO * 16; e += blockDim.x) {
-        float v = 0.0f;
-        for (int w = 0; w < wpb; w++) v += red[w * 9 * CO * 16 + e];
-        const int t = e / (CO * 16), oi = e - t * (CO * 16);
-        if (a.part) a.part[(size_t)blockIdx.x * (9 * CO * 16) + (size_t)oi * 9 + t] = v;
-        else atomicAdd(a.dw + (size_t)oi * 9 + t, v);  // [out][in][tap]
-    }
+    // ---- the block's partial sums -> one
+    pol_wgrad_reduce<NH>(acc, (float*)lds, wave, wpb, lane, a.dw, a.part, 9 * CO * 16);
 }
 
 // One weight gradient: the launch (two waves per block, at most four blocks = two waves per SIMD on a CU) and, in deterministic mode,
@@ -1211,11 +924,7 @@ template <int GO, int CO, bool FROM_CODES>
 static hipError_t launch_front_wgrad(WgradArgs a, int n_cus, int device_id, hipStream_t st) {
     const int wpb = 2;
     const size_t sh = pol_wgrad_block_bytes(GO, CO, wpb);
-    int per_cu = (int)((160 * 1024) / sh);
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 4) per_cu = 4;
-    int64_t blocks = (a.S + wpb - 1) / wpb;
-    if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
+    const int64_t blocks = pol_blocks(a.S, wpb, sh, n_cus, 4);
     const DetWorkspace det = ctf_policy_det(device_id);
     a.part = det.ptr;
     if (a.part && blocks * 9 * CO * 16 > det.floats) return POL_WORKSPACE_TOO_SMALL;
@@ -1227,12 +936,12 @@ static hipError_t launch_front_wgrad(WgradArgs a, int n_cus, int device_id, hipS
 extern "C" int ctf_policy_front_wgrad(const uint16_t* dz2_dev, const uint16_t* h1_dev, const uint16_t* dz1_dev, const uint8_t* codes_dev,
                                       int64_t n_samples, int32_t grid_size, float* dw2_dev, float* dw1_dev, int32_t device_id, void* stream) {
     if (!dz2_dev || !h1_dev || !dz1_dev || !codes_dev || !dw2_dev || !dw1_dev) return ctf_policy_fail("null argument");
-    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (pol_train_check(grid_size, n_samples, 0, INT64_MAX)) return -1;
     if (((uintptr_t)dz2_dev | (uintptr_t)h1_dev | (uintptr_t)dz1_dev) & 15) return ctf_policy_fail("16-byte alignment");
     if (!n_samples) return 0;
-    const int n_cus = ctf_policy_cus(device_id);
-    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    PolTrainSetup t;  // (these kernels divide by constants: the reciprocals go unused)
+    if (pol_train_setup(grid_size, device_id, &t)) return -1;
+    const int n_cus = t.n_cus;
     DeviceScope scope(device_id);
     if (scope.error) return ctf_policy_fail(scope.error);
     hipStream_t st = (hipStream_t)stream;
@@ -1257,25 +966,24 @@ extern "C" int ctf_policy_front_backward(const uint16_t* d_act_dev, const uint16
                                          uint16_t* dz1_dev, float* dw2_dev, float* dw1_dev, float* bias2_grad_dev, float* bias1_grad_dev,
                                          int32_t device_id, void* stream) {
     if (!d_act_dev || !act_dev || !h1_dev || !codes_dev || !conv2_t_frag_dev || !dz1_dev || !dw2_dev || !dw1_dev) return ctf_policy_fail("null argument");
-    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 0) return ctf_policy_fail("n_samples out of range");
+    if (pol_train_check(grid_size, n_samples, 0, INT64_MAX)) return -1;
     if (((uintptr_t)d_act_dev | (uintptr_t)act_dev) & 7) return ctf_policy_fail("8-byte alignment");
     if (((uintptr_t)h1_dev | (uintptr_t)conv2_t_frag_dev | (uintptr_t)dz1_dev) & 15) return ctf_policy_fail("h1_dev / conv2_t_frag_dev / dz1_dev must be 16-byte aligned");
     if (!n_samples) return 0;
+    PolTrainSetup t;
+    if (pol_train_setup(grid_size, device_id, &t)) return -1;
+    const int n_cus = t.n_cus;
     DgradArgs a;
     a.d_act = d_act_dev; a.act = act_dev; a.h1 = h1_dev; a.w2t = (const u32x4_t*)conv2_t_frag_dev; a.dz2 = nullptr; a.dz1 = dz1_dev;
     a.db2 = bias2_grad_dev; a.db1 = bias1_grad_dev; a.dw2 = dw2_dev; a.S = n_samples; a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
-    const int n_cus = ctf_policy_cus(device_id);
-    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    a.inv_g1 = t.inv_g1; a.inv_g2 = t.inv_g2;
     DeviceScope scope(device_id);
     if (scope.error) return ctf_policy_fail(scope.error);
     hipStream_t st = (hipStream_t)stream;
     // the fused pass: four waves per block, one block per CU (the padded images are 25 KB per wave, the registers one wave per SIMD)
     const int wpb = 4;
     const size_t sh = pol_dgrad_block_bytes(grid_size, true, wpb);
-    int64_t blocks = (n_samples + wpb - 1) / wpb;
-    if (blocks > (int64_t)n_cus) blocks = n_cus;
+    const int64_t blocks = pol_blocks(n_samples, wpb, sh, n_cus, 1);
     const DetWorkspace det = ctf_policy_det(device_id);
     a.part = det.ptr;
     if (a.part && blocks * DGRAD_PART > det.floats) return pol_finish(POL_WORKSPACE_TOO_SMALL);
@@ -1293,31 +1001,20 @@ extern "C" int ctf_policy_features_train(const uint8_t* codes_dev, const uint16_
                                          uint16_t* h1_dev, int32_t device_id, void* stream) {
     if (!codes_dev || !meta_dev || !conv1_frag_dev || !conv1_bias_dev || !conv2_frag_dev || !conv2_bias_dev || !act_dev || !h1_dev)
         return ctf_policy_fail("null argument");
-    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
-    if (n_samples < 1 || n_samples > 0x7FFFFFFF) return ctf_policy_fail("n_samples out of range");
+    if (pol_train_check(grid_size, n_samples, 1, 0x7FFFFFFF)) return -1;
     if (meta_len < 2 || (meta_len & 1)) return ctf_policy_fail("meta_len must be even (2N + 6)");
     if (((uintptr_t)act_dev & 15) || ((uintptr_t)h0_dev & 15) || ((uintptr_t)h1_dev & 15) || ((uintptr_t)meta_dev & 3))
         return ctf_policy_fail("act_dev / h0_dev / h1_dev must be 16-byte, meta_dev 4-byte aligned");
-    PolicyArgs a;
-    a.codes = codes_dev; a.meta = meta_dev; a.act = act_dev;
-    a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
-    a.w2frag = (const u32x4_t*)conv2_frag_dev; a.b2 = conv2_bias_dev;
-    a.n_envs = (int32_t)n_samples; a.N = 1; a.G = grid_size; a.M = meta_len; a.n_sel = 1;  // every row of codes_dev is one sample
-    a.Kp = ctf_policy_act_stride(grid_size, meta_len);
-    a.sel_pack = 0;
-    a.h0_out = h0_dev; a.h1_out = h1_dev;
-    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
-    const int n_cus = ctf_policy_cus(device_id);
-    if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
+    PolTrainSetup t;
+    if (pol_train_setup(grid_size, device_id, &t)) return -1;
+    // every row of codes_dev is one sample: n_samples envs of one agent, selection slot 0 = agent 0
+    const PolicyArgs a = pol_front_args(codes_dev, meta_dev, act_dev, conv1_frag_dev, conv1_bias_dev, conv2_frag_dev, conv2_bias_dev, (int32_t)n_samples, 1,
+                                        grid_size, meta_len, 1, 0, ctf_policy_act_stride(grid_size, meta_len), t.inv_g1, t.inv_g2, h0_dev, h1_dev);
     DeviceScope scope(device_id);
     if (scope.error) return ctf_policy_fail(scope.error);
-    const int per_wave = pol_h0_bytes(grid_size) + pol_h1_bytes(grid_size);
     const int wpb = 4;
-    const size_t sh = (size_t)wpb * per_wave;
-    int per_cu = (int)((160 * 1024) / sh);
-    if (per_cu * wpb > 12) per_cu = 12 / wpb;  // 3 waves per SIMD, as in ctf_policy_features
-    int64_t blocks = (n_samples + wpb - 1) / wpb;
-    if (blocks > (int64_t)n_cus * per_cu) blocks = (int64_t)n_cus * per_cu;
+    const size_t sh = (size_t)wpb * (pol_h0_bytes(grid_size) + pol_h1_bytes(grid_size));
+    const int64_t blocks = pol_blocks(n_samples, wpb, sh, t.n_cus, 12 / wpb);  // 3 waves per SIMD, as in ctf_policy_features
     return pol_finish(pol_launch(grid_size == 15 ? k_policy_features<15, true> : k_policy_features<11, true>, blocks, wpb * WAVE, sh, (hipStream_t)stream, a));
 }
 

@@ -11,8 +11,10 @@
 
 #define WAVE 64
 // Profiling-only ablations (never defined in the shipped build; tools/ablate_policy.sh):
-//   bit0 no activation stores, bit1 no exp/rcp in tanh, bit2 no h0 update, bit3 every operand read from one LDS address,
-//   bit4 every sample of a wave stored to the same row (store instructions without the HBM traffic),
+//   bit0 nothing stored behind a conv2 tile pair (ctf_policy_front_dev.h: the activation stores of all three forward kernels, and
+//   the factored kernel's h2s), bit1 no exp/rcp in tanh (every kernel), bit2 no h0 update (k_policy_features), bit3 every operand of
+//   the shared conv1 pass and of the conv2 tile pairs read from one LDS address (all three forward kernels),
+//   bit4 every sample of a wave stored to the same row (store instructions without the HBM traffic; k_policy_features),
 //   bit5 team kernel: half of the shared activation stores skipped, bit6 team kernel: rows env-major
 #ifndef POL_ABLATE
 #define POL_ABLATE 0

@@ -19,6 +19,7 @@
 //                                   y1[agent] = bf16(D + (W_flat . h2_v)[env] + b) — the pre-activation ctf_policy_head consumes
 //
 // The view GEMM itself ([E][32 * PP] x [32 * PP][256], fp32 out) is the BLAS library's (policy_native.py).
+#include "ctf_policy_front_dev.h"
 #include "ctf_policy_host.h"
 
 #define FACT_MT 128      // slots per tile
@@ -216,31 +217,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     constexpr int H0A = GG * 16;
     const int H1A = pol_h1_bytes(G) / 2;
 
-    u32x4_t w1[5], w2[9];
+    // This kernel keeps its own text of pol_front_prologue (ctf_policy_front_dev.h; the same values): through the helper the compiler
+    // schedules the conv loops of the <11> instantiation differently (117 -> 109 s_waitcnt in the listing)
+    PolFront f;
 #pragma unroll
-    for (int s = 0; s < 5; s++) w1[s] = a.w1frag[s * WAVE + lane];
+    for (int s = 0; s < 5; s++) f.w1[s] = a.w1frag[s * WAVE + lane];
 #pragma unroll
-    for (int t = 0; t < 9; t++) w2[t] = a.w2frag[t * WAVE + lane];
-    f32x4_t bias1;
+    for (int t = 0; t < 9; t++) f.w2[t] = a.w2frag[t * WAVE + lane];
 #pragma unroll
-    for (int r = 0; r < 4; r++) bias1[r] = a.b1[(lane >> 4) * 4 + r];
-    f32x16_t bias2;
+    for (int r = 0; r < 4; r++) f.bias1[r] = a.b1[(lane >> 4) * 4 + r];
 #pragma unroll
-    for (int r = 0; r < 16; r++) bias2[r] = a.b2[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-
-    const int n1 = lane & 15, g1 = lane >> 4;
-    int off1[5], tap1[5];
+    for (int r = 0; r < 16; r++) f.bias2[r] = a.b2[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
+    f.n1 = lane & 15, f.g1 = lane >> 4;
+    int tap1[5];
 #pragma unroll
     for (int s = 0; s < 5; s++) {
-        tap1[s] = min(2 * s + (g1 >> 1), 8);  // "tap 9" has zero weights: any valid address
-        off1[s] = ((tap1[s] / 3) * G + (tap1[s] % 3)) * 16 + (g1 & 1) * H0A;
+        tap1[s] = min(2 * s + (f.g1 >> 1), 8);  // "tap 9" has zero weights: any valid address
+        f.off1[s] = ((tap1[s] / 3) * G + (tap1[s] % 3)) * 16 + (f.g1 & 1) * H0A;
     }
-    const int y1_0 = (int)(((uint32_t)n1 * a.inv_g1) >> 16), x1_0 = n1 - y1_0 * G1;
-    constexpr int dy1 = 16 / G1, dx1 = 16 - dy1 * G1;
-    uint8_t* h1w = h1 + (g1 >> 1) * H1A + n1 * 16 + (g1 & 1) * 8;
-    const int n2 = lane & 31, hh = lane >> 5;
-    const int j1 = min(n1, 8), pdy1 = j1 / 3, pdx1 = j1 - 3 * pdy1;
-    const int j2 = min(n2, 24), pdy2 = j2 / 5, pdx2 = j2 - 5 * pdy2;
+    f.y1_0 = (int)(((uint32_t)f.n1 * a.inv_g1) >> 16), f.x1_0 = f.n1 - f.y1_0 * G1;
+    f.dy1 = 16 / G1, f.dx1 = 16 - f.dy1 * G1;
+    f.h1w = h1 + (f.g1 >> 1) * H1A + f.n1 * 16 + (f.g1 & 1) * 8;
+    f.n2 = lane & 31, f.hh = lane >> 5;
+    const int j1 = min(f.n1, 8), pdy1 = j1 / 3, pdx1 = j1 - 3 * pdy1;
+    const int j2 = min(f.n2, 24), pdy2 = j2 / 5, pdx2 = j2 - 5 * pdy2;
 
     const int e_first = blockIdx.x * wpb + wave, e_stride = gridDim.x * wpb;
     const int ag0 = (int)(a.sel_pack & 15u);
@@ -295,48 +295,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         FACT_STAMP(1);
 
         // ---- 2. shared conv1 + tanh -> h1 (two tiles in flight)
-        constexpr int T1 = (FACT_ABLATE & 16) ? 0 : ((P1 + 15) >> 4);
-        int x1 = x1_0, cell1 = y1_0 * G + x1_0;
-        int t = 0;
-#pragma unroll 1
-        for (; t + 1 < T1; t += 2) {
-            const uint8_t* base_a = h0 + cell1 * 16;
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            const uint8_t* base_b = h0 + cell1 * 16;
-            x1 += dx1;
-            cell1 += dy1 * G + dx1;
-            if (x1 >= G1) { x1 -= G1; cell1 += G - G1; }
-            f32x4_t acc_a = bias1, acc_b = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                const u32x4_t bb = *(const u32x4_t*)(base_b + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(bb), acc_b, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;
-            o[0] = tanh2_pack(acc_b[0], acc_b[1]);
-            o[1] = tanh2_pack(acc_b[2], acc_b[3]);
-            *(u32x2_t*)(h1w + 16 * (t + 1) * 16) = o;
-        }
-        if (t < T1) {
-            const uint8_t* base_a = h0 + cell1 * 16;
-            f32x4_t acc_a = bias1;
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off1[q]);
-                acc_a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(ba), acc_a, 0, 0, 0);
-            }
-            u32x2_t o;
-            o[0] = tanh2_pack(acc_a[0], acc_a[1]);
-            o[1] = tanh2_pack(acc_a[2], acc_a[3]);
-            *(u32x2_t*)(h1w + 16 * t * 16) = o;
-        }
+        pol_conv1_pass(f, h0, G, (FACT_ABLATE & 16) ? 0 : ((P1 + 15) >> 4));
         FACT_STAMP(2);
         // This env's own cells / metadata / slots and the next env's codes, issued at the top (this also drains the previous env's
         // stores, which have had the whole of conv1 to land).
@@ -370,25 +329,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                 const int cy1 = min(max(oy1, 0), G1 - 1), cx1 = min(max(ox1, 0), G1 - 1);
                 base[k] = h0 + (cy1 * G + cx1) * 16;
                 const int ty = syv[k] - cy1, tx = sxv[k] - cx1;  // the tap of this lane's output that reads the own cell
-                own_tap[k] = ((unsigned)ty < 3u && (unsigned)tx < 3u && !(g1 & 1)) ? 3 * ty + tx : -1;  // (channel 0 sits in half 0)
-                acc[k] = bias1;
+                own_tap[k] = ((unsigned)ty < 3u && (unsigned)tx < 3u && !(f.g1 & 1)) ? 3 * ty + tx : -1;  // (channel 0 sits in half 0)
+                acc[k] = f.bias1;
             }
 #pragma unroll
             for (int q = 0; q < 5; q++) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    u32x4_t b = *(const u32x4_t*)(base[k] + off1[q]);
+                    u32x4_t b = *(const u32x4_t*)(base[k] + f.off1[q]);
                     b[0] |= (own_tap[k] == tap1[q]) ? 0x3F80u : 0u;  // channel 0 of the own cell = 1.0
-                    acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w1[q]), as_bf16x8(b), acc[k], 0, 0, 0);
+                    acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(f.w1[q]), as_bf16x8(b), acc[k], 0, 0, 0);
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                u32x2_t o;
-                o[0] = tanh2_pack(acc[k][0], acc[k][1]);
-                o[1] = tanh2_pack(acc[k][2], acc[k][3]);
-                if (n1 < 9) *(u32x2_t*)(hp + k * HPB + n1 * 32 + g1 * 8) = o;  // channels 4 g1 .. 4 g1 + 3 of patch position n1
-            }
+            for (int k = 0; k < 4; k++)
+                if (f.n1 < 9) *(u32x2_t*)(hp + k * HPB + f.n1 * 32 + f.g1 * 8) = pol_tanh4(acc[k]);  // channels 4 g1 .. 4 g1 + 3 of patch position n1
         }
 
         __builtin_amdgcn_s_waitcnt(0xC07F);  // every lane's conv1 operands have been read: h2s may overwrite h0
@@ -400,35 +355,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         static_assert((T2 & 1) == 0, "tile pairs");
 #pragma unroll 1
         for (int t2 = 0; t2 < T2; t2 += 2) {
-            const int pa = 32 * t2 + n2, pb = pa + 32;
-            const int pca = min(pa, P2 - 1), pcb = min(pb, P2 - 1);
-            const int ya = (int)(((uint32_t)pca * a.inv_g2) >> 16), yb = (int)(((uint32_t)pcb * a.inv_g2) >> 16);
-            const uint8_t* base_a = h1 + (ya * G1 + (pca - ya * G2)) * 16 + hh * H1A;
-            const uint8_t* base_b = h1 + (yb * G1 + (pcb - yb * G2)) * 16 + hh * H1A;
-            f32x16_t acc_a = bias2, acc_b = bias2;
-#pragma unroll
-            for (int tap = 0; tap < 9; tap++) {
-                const int off = ((tap / 3) * G1 + (tap % 3)) * 16;
-                const u32x4_t ba = *(const u32x4_t*)(base_a + off);
-                const u32x4_t bb = *(const u32x4_t*)(base_b + off);
-                acc_a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(ba), acc_a, 0, 0, 0);
-                acc_b = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(bb), acc_b, 0, 0, 0);
-            }
-            const uint32_t lane_off = (uint32_t)(((3 + hh) * PP + pa) * 8);  // the four channel groups sit (2 q - 3) * PP * 8 around it
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                u32x2_t oa, ob;
-                oa[0] = tanh2_pack(acc_a[4 * q], acc_a[4 * q + 1]);
-                oa[1] = tanh2_pack(acc_a[4 * q + 2], acc_a[4 * q + 3]);
-                ob[0] = tanh2_pack(acc_b[4 * q], acc_b[4 * q + 1]);
-                ob[1] = tanh2_pack(acc_b[4 * q + 2], acc_b[4 * q + 3]);
+            const int pa = 32 * t2 + f.n2, pb = pa + 32;
+            const uint32_t lane_off = (uint32_t)(((3 + f.hh) * PP + pa) * 8);  // the four channel groups sit (2 q - 3) * PP * 8 around it
+            pol_conv2_pair(f, h1, H1A, G, a.inv_g2, t2, [&](int q, u32x2_t oa, u32x2_t ob) {
                 if (!(FACT_ABLATE & 1)) {
                     *(u32x2_t*)(vrow + lane_off + (2 * q - 3) * PP * 8) = oa;
                     *(u32x2_t*)(vrow + lane_off + (2 * q - 3) * PP * 8 + 256) = ob;
                 }
-                *(u32x2_t*)(h2s + pa * H2R + (8 * q + 4 * hh) * 2) = oa;  // channels 8 q + 4 hh .. + 3 of position pa
-                *(u32x2_t*)(h2s + pb * H2R + (8 * q + 4 * hh) * 2) = ob;
-            }
+                *(u32x2_t*)(h2s + pa * H2R + (8 * q + 4 * f.hh) * 2) = oa;  // channels 8 q + 4 hh .. + 3 of position pa
+                *(u32x2_t*)(h2s + pb * H2R + (8 * q + 4 * f.hh) * 2) = ob;
+            });
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -447,14 +383,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                 ok2[k] = (unsigned)oy2 < (unsigned)G2 && (unsigned)ox2 < (unsigned)G2;
                 const int cy2 = min(max(oy2, 0), G2 - 1), cx2 = min(max(ox2, 0), G2 - 1);
                 cpos[k] = cy2 * G2 + cx2;
-                shared_base[k] = h1 + (cy2 * G1 + cx2) * 16 + hh * H1A;
+                shared_base[k] = h1 + (cy2 * G1 + cx2) * 16 + f.hh * H1A;
                 const int r0y = cy2 - (syv[k] - 2), r0x = cx2 - (sxv[k] - 2);  // this lane's top-left input, relative to the 3 x 3 patch
                 // rows ty (columns tx) in 0..2 with 0 <= r0 + t <= 2, as 3-bit sets
                 const uint32_t rb = (r0y <= 0 ? (7u << min(-r0y, 3)) : (7u >> min(r0y, 3))) & 7u;
                 const uint32_t cb = (r0x <= 0 ? (7u << min(-r0x, 3)) : (7u >> min(r0x, 3))) & 7u;
                 pmask[k] = cb * ((rb & 1u) + 8u * ((rb >> 1) & 1u) + 64u * (rb >> 2));
-                priv_base[k] = hp + k * HPB + (r0y * 3 + r0x) * 32 + hh * 16;
-                acc[k] = bias2;
+                priv_base[k] = hp + k * HPB + (r0y * 3 + r0x) * 32 + f.hh * 16;
+                acc[k] = f.bias2;
             }
 #pragma unroll
             for (int tap = 0; tap < 9; tap++) {
@@ -464,7 +400,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                     const bool patched = !(FACT_ABLATE & 4) && ((pmask[k] >> tap) & 1u);
                     const uint8_t* src = patched ? priv_base[k] + (ty * 3 + tx) * 32 : shared_base[k] + (ty * G1 + tx) * 16;
                     const u32x4_t b = *(const u32x4_t*)src;
-                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(w2[tap]), as_bf16x8(b), acc[k], 0, 0, 0);
+                    acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(f.w2[tap]), as_bf16x8(b), acc[k], 0, 0, 0);
                 }
             }
             // The rows leave through LDS: written straight from the accumulator layout they would be 8-byte pieces 64 bytes apart — 200
@@ -475,11 +411,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
             for (int k = 0; k < 4; k++) {
                 if (k < A) {
                     uint8_t* const prow_l = pst + k * PSTB;
-                    const uint8_t* sh = h2s + cpos[k] * H2R + 8 * hh;
+                    const uint8_t* sh = h2s + cpos[k] * H2R + 8 * f.hh;
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         const u32x2_t s2 = *(const u32x2_t*)(sh + 16 * q);
-                        const uint32_t p0 = tanh2_pack(acc[k][4 * q], acc[k][4 * q + 1]), p1 = tanh2_pack(acc[k][4 * q + 2], acc[k][4 * q + 3]);
+                        const u32x2_t pq = pol_tanh4(acc[k], q);
+                        const uint32_t p0 = pq[0], p1 = pq[1];
                         u32x2_t d;
                         d[0] = pack_bf16(__uint_as_float(p0 << 16) - __uint_as_float(s2[0] << 16),
                                          __uint_as_float(p0 & 0xFFFF0000u) - __uint_as_float(s2[0] & 0xFFFF0000u));
@@ -487,18 +424,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
                                          __uint_as_float(p1 & 0xFFFF0000u) - __uint_as_float(s2[1] & 0xFFFF0000u));
                         if (FACT_ABLATE & 2) d = (u32x2_t){p0 ^ s2[0], p1};
                         if (!ok2[k]) d = (u32x2_t){0u, 0u};  // a patch position outside the image: its weights are zero too
-                        if (n2 < 25) *(u32x2_t*)(prow_l + n2 * H2R + (8 * q + 4 * hh) * 2) = d;
+                        if (f.n2 < 25) *(u32x2_t*)(prow_l + f.n2 * H2R + (8 * q + 4 * f.hh) * 2) = d;
                     }
-                    if (lane < mpairs) {  // metadata (f16 -> bf16) behind the patch values, zeros up to the row's end
-                        const uint32_t mw = metaw[k];
-                        uint32_t out = 0;
-                        if (lane < (a.M >> 1)) {
-                            const float lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(mw & 0xFFFFu));
-                            const float hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(mw >> 16));
-                            out = pack_bf16(lo, hi);
-                        }
-                        ((uint32_t*)(prow_l + 25 * H2R))[lane] = out;
-                    }
+                    // metadata (f16 -> bf16) behind the patch values, zeros up to the row's end
+                    if (lane < mpairs) ((uint32_t*)(prow_l + 25 * H2R))[lane] = pol_meta_word(metaw[k], lane, a.M, false);
                 }
             }
             __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -787,14 +716,12 @@ extern "C" int ctf_policy_features_fact(const uint8_t* codes_dev, const uint16_t
     if (fact_geometry(grid_size, meta_len, &fa.KV, &fa.KR)) return -1;
     if (n_envs < 1 || n_agents < 1 || n_agents > 16) return ctf_policy_fail("n_envs / n_agents out of range");
     if (((uintptr_t)view_dev & 15) || ((uintptr_t)prow_dev & 15) || ((uintptr_t)meta_dev & 3)) return ctf_policy_fail("view / prow must be 16-byte, meta 4-byte aligned");
-    PolicyArgs& a = fa.p;
-    if (pol_pack_sel(agent_sel, n_sel, n_agents, 4, &a.sel_pack)) return -1;
-    a.codes = codes_dev; a.meta = meta_dev; a.act = nullptr;
-    a.w1frag = (const u32x4_t*)conv1_frag_dev; a.b1 = conv1_bias_dev;
-    a.w2frag = (const u32x4_t*)conv2_frag_dev; a.b2 = conv2_bias_dev;
-    a.n_envs = n_envs; a.N = n_agents; a.G = grid_size; a.M = meta_len; a.n_sel = n_sel; a.Kp = 0;
-    a.h0_out = nullptr; a.h1_out = nullptr;
-    if (pol_recips(grid_size, &a.inv_g1, &a.inv_g2)) return -1;
+    uint64_t sel_pack;
+    uint32_t inv_g1, inv_g2;
+    if (pol_pack_sel(agent_sel, n_sel, n_agents, 4, &sel_pack)) return -1;
+    if (pol_recips(grid_size, &inv_g1, &inv_g2)) return -1;
+    fa.p = pol_front_args(codes_dev, meta_dev, nullptr, conv1_frag_dev, conv1_bias_dev, conv2_frag_dev, conv2_bias_dev, n_envs, n_agents, grid_size, meta_len,
+                          n_sel, sel_pack, 0, inv_g1, inv_g2, nullptr, nullptr);
     fa.selfcells = selfcell_dev; fa.slot_of = slot_of_dev; fa.view = view_dev; fa.prow = prow_dev; fa.A = n_sel;
     const int n_cus = ctf_policy_cus(device_id);
     if (!n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
@@ -803,11 +730,8 @@ extern "C" int ctf_policy_features_fact(const uint8_t* codes_dev, const uint16_t
     // two blocks of four waves per CU = two waves per SIMD (16.7 KB of LDS per wave since h2s lies over h0)
     const int wpb = pol_env_int("CTF_POLICY_FACT_WPB", 1, 4, 4);  // profiling only
     const size_t sh = (size_t)wpb * pol_fact_wave_bytes(grid_size);
-    int per_cu = (int)((160 * 1024) / sh);
-    if (per_cu < 1) per_cu = 1;
-    per_cu = pol_env_int("CTF_POLICY_FACT_BLOCKS_PER_CU", 1, per_cu, per_cu);  // profiling only
-    int blocks = (n_envs + wpb - 1) / wpb;
-    if (blocks > n_cus * per_cu) blocks = n_cus * per_cu;
+    const int per_cu_cap = pol_env_int("CTF_POLICY_FACT_BLOCKS_PER_CU", 1, 0x7FFFFFFF, 0x7FFFFFFF);  // profiling only; otherwise what the LDS takes
+    const int64_t blocks = pol_blocks(n_envs, wpb, sh, n_cus, per_cu_cap);
     return pol_finish(pol_launch(grid_size == 15 ? k_policy_features_fact<15> : k_policy_features_fact<11>, blocks, wpb * WAVE, sh, (hipStream_t)stream, fa));
 }
 

@@ -64,7 +64,8 @@ static inline int pol_recips(int grid_size, uint32_t* inv_g1, uint32_t* inv_g2) 
 }
 
 // agent_sel[0 .. n_sel-1] -> nibble k = agent index of selection slot k.  0, or -1 with the error set.  (max_sel 16: ctf_policy_features,
-// which has checked the list and its length before; 4: the factored path, which has not.)
+// which has checked the list and its length before; 4: the factored path, which has not — the one error text names the factored path
+// whatever max_sel is.)
 static inline int pol_pack_sel(const int32_t* agent_sel, int n_sel, int n_agents, int max_sel, uint64_t* out) {
     if (!agent_sel || n_sel < 1 || n_sel > max_sel) return ctf_policy_fail("the factored path takes 1..4 selected agents");
     uint64_t p = 0;
@@ -73,5 +74,50 @@ static inline int pol_pack_sel(const int32_t* agent_sel, int n_sel, int n_agents
         p |= (uint64_t)agent_sel[k] << (4 * k);
     }
     *out = p;
+    return 0;
+}
+
+// The arguments of a forward kernel of the front (h0_out / h1_out: the training instantiation's, else NULL).
+static inline PolicyArgs pol_front_args(const uint8_t* codes, const uint16_t* meta, uint16_t* act, const void* conv1_frag, const float* conv1_bias,
+                                        const void* conv2_frag, const float* conv2_bias, int n_envs, int n_agents, int grid_size, int meta_len,
+                                        int n_sel, uint64_t sel_pack, int Kp, uint32_t inv_g1, uint32_t inv_g2, uint16_t* h0_out, uint16_t* h1_out) {
+    PolicyArgs a;
+    a.codes = codes; a.meta = meta; a.act = act;
+    a.w1frag = (const u32x4_t*)conv1_frag; a.b1 = conv1_bias;
+    a.w2frag = (const u32x4_t*)conv2_frag; a.b2 = conv2_bias;
+    a.n_envs = n_envs; a.N = n_agents; a.G = grid_size; a.M = meta_len; a.Kp = Kp; a.n_sel = n_sel;
+    a.sel_pack = sel_pack;
+    a.inv_g1 = inv_g1; a.inv_g2 = inv_g2;
+    a.h0_out = h0_out; a.h1_out = h1_out;
+    return a;
+}
+
+// Blocks of a launch whose waves each take one item at a time (a sample, an env): enough for all items at `wpb` waves a block, at most
+// what the device holds at once — per CU as many blocks as 160 KiB of LDS take at `lds_bytes` each (at least one), capped at `per_cu_cap`.
+static inline int64_t pol_blocks(int64_t items, int wpb, size_t lds_bytes, int n_cus, int per_cu_cap) {
+    int64_t per_cu = (int64_t)((160 * 1024) / lds_bytes);
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > per_cu_cap) per_cu = per_cu_cap;
+    const int64_t blocks = (items + wpb - 1) / wpb;
+    return blocks < n_cus * per_cu ? blocks : n_cus * per_cu;
+}
+
+// The preamble of the training front's entry points, in two halves because every entry point's own alignment checks (and its early
+// return for zero samples) sit between them: the argument checks, ..
+static inline int pol_train_check(int grid_size, int64_t n_samples, int64_t n_min, int64_t n_max) {
+    if (grid_size != 15 && grid_size != 11) return ctf_policy_fail("the training front is built for grid_size 11 and 15 (the reference's maps)");
+    if (n_samples < n_min || n_samples > n_max) return ctf_policy_fail("n_samples out of range");
+    return 0;
+}
+// .. and what the launch sizing needs: the kernels' reciprocals and the device's compute units.  (The DeviceScope that follows is the
+// entry point's own: it lives until its return.)
+struct PolTrainSetup {
+    uint32_t inv_g1, inv_g2;
+    int n_cus;
+};
+static inline int pol_train_setup(int grid_size, int device_id, PolTrainSetup* t) {
+    if (pol_recips(grid_size, &t->inv_g1, &t->inv_g2)) return -1;
+    t->n_cus = ctf_policy_cus(device_id);
+    if (!t->n_cus) return ctf_policy_fail("hipGetDeviceProperties failed");
     return 0;
 }

@@ -143,6 +143,53 @@ def test_factored_fc1_matches_its_float64_emulation(g, c, n, e, sel):
     assert bool((d_old <= 2 * ulp_bf16(want) + 2e-2).all()) and float((d_old > ulp_bf16(want) + 4e-3).double().mean()) < 0.1
 
 
+@pytest.mark.parametrize("g,c,n,e,sel", [(15, 14, 8, 65, [0, 1, 2, 3]), (11, 8, 4, 65, [3, 1])])
+def test_view_and_patch_rows_equal_the_per_agent_kernels_values_bit_for_bit(g, c, n, e, sel):
+    """k_policy_features_fact's header: "view and patch values equal that kernel's [k_policy_features'] bit for bit".  The view row is the
+    per-agent kernel's activation row of the codes without own-position bits; a patch value is the float32 difference of the per-agent
+    kernel's two bf16 values at that position, rounded to bf16; positions of the 5 x 5 patch outside the image are zero.  Own cells in
+    the corners (envs 0 and 2) and in row / column 1 (env 1): patches the image border clips.  65 envs: 16 blocks of four waves and one
+    wave alone."""
+    rng = np.random.default_rng(100 * g + e)
+    m, g2 = 2 * n + 6, g - 4
+    pp = (g2 * g2 + 31) // 32 * 32
+    cells = np.stack([rng.permutation(g * g)[:n] for _ in range(e)])
+    corners = [0, g - 1, g * (g - 1), g * g - 1]
+    edge = [1 * g + 1, 1 * g + (g - 2), (g - 2) * g + 1, (g // 2) * g + 1]
+    for ki, k in enumerate(sel):
+        cells[0, k], cells[1, k], cells[2, k] = corners[ki], edge[ki], corners[(ki + 2) % 4]
+    codes, cells = team_codes(rng, e, n, g, c, cells=cells)
+    metas = rng.random((e, n, m)).astype(np.float16)
+    net = fill_(native.CtfPolicyNative(9, c, g, m)).cuda()
+    dev = lambda a: torch.tensor(a, device="cuda")
+    net.fc1_from_codes_factored(dev(codes), dev(metas), sel, dev(cells))
+    b = net._act_bufs[("fact", e, len(sel), 0)]
+    view, prow, slot_of = b["view"].cpu(), b["prow"].cpu(), b["slot_of"].cpu().long()
+    full = net.features_from_codes(dev(codes), dev(metas), sel, shared_view=False).cpu()
+    flat = net.features_from_codes(dev(codes & 0x7F), dev(metas), [sel[0]], shared_view=False).cpu()
+    assert view.dtype == prow.dtype == full.dtype == torch.bfloat16
+    assert torch.equal(view[:, :32 * pp], flat[:, :32 * pp])                       # padding positions included
+    ch = torch.arange(32)
+    col0 = (ch // 4) * pp * 4 + ch % 4                                             # element (c, p) sits at column ((c // 4) * PP + p) * 4 + c % 4
+    inside_seen = outside_seen = 0
+    for ki, k in enumerate(sel):
+        rows = prow[slot_of[ki * e:(ki + 1) * e]]                                  # the patch rows of agent k, env by env
+        full_k = full[ki * e:(ki + 1) * e]
+        sy, sx = cells[:, k].astype(np.int64) // g, cells[:, k].astype(np.int64) % g
+        for j in range(25):
+            oy, ox = sy - 4 + j // 5, sx - 4 + j % 5
+            ok = torch.tensor((oy >= 0) & (oy < g2) & (ox >= 0) & (ox < g2))
+            cols = col0[None, :] + 4 * torch.tensor(np.clip(oy, 0, g2 - 1) * g2 + np.clip(ox, 0, g2 - 1))[:, None]
+            want = (full_k.gather(1, cols).float() - flat.gather(1, cols).float()).bfloat16()
+            want[~ok] = 0                                                          # outside the image: zeros
+            assert torch.equal(rows[:, 32 * j:32 * j + 32], want), (k, j)
+            inside_seen += int(ok.sum())
+            outside_seen += int((~ok).sum())
+        assert torch.equal(rows[:, 800:800 + m], full_k[:, 32 * pp:32 * pp + m])
+        assert not bool(rows[:, 800 + m:].float().abs().any())
+    assert inside_seen > 0 and outside_seen >= 16 * len(sel)                       # the corner patches alone are 16 positions outside each
+
+
 def test_buckets_are_a_partition_into_padded_tiles_by_own_cell():
     rng = np.random.default_rng(5)
     g, c, n, e = 15, 14, 8, 3001
