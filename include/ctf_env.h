@@ -13,7 +13,8 @@
  *     the library never allocates or frees I/O buffers;
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
- *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset and ctf_harvest_episodes are kernel launches and nothing else (no
+ *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation and
+ *     ctf_export_visitation are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -55,7 +56,8 @@ extern "C" {
                                    the step of its envs and went on (the launch's blocks did not run in index order)  */
 #define CTF_ST_BAD_SNAPSHOT 32u /* ctf_load_states: a record's header or destination index was wrong; that env is untouched
                                    (ctf_save_states: a source index outside [0, E); that record's header is left invalid)      */
-#define CTF_ST_BAD_GROUP 64u    /* ctf_harvest_episodes: a group id outside [0, n_groups); that env is skipped                 */
+#define CTF_ST_BAD_GROUP 64u    /* ctf_harvest_episodes / ctf_harvest_visitation: a group id outside [0, n_groups); that env is skipped
+                                   (ctf_export_visitation: an env index outside [0, E); that record is not written)             */
 
 /* ctf_config.rng_mode */
 #define CTF_RNG_MT19937 0 /* the reference's two MT19937 generators, bit for bit (default)                          */
@@ -329,6 +331,27 @@ int ctf_load_states(ctf_env* env, const uint8_t* src_dev, const int32_t* dst_idx
 int32_t ctf_harvest_words(const ctf_env* env);
 int ctf_harvest_episodes(ctf_env* env, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
                          int64_t* acc_dev, void* stream);
+
+/* Visitation maps in bulk, on the device (ctf_visitation.h has the definition): metrics['agent_visitation_maps'] of many envs
+ * without a ctf_get_state round trip per env.  THE MAP OF ONE ENV is what ctf_get_state's view holds before its u8 wrap: the base
+ * maps (zeros + 1 at the start cells after a reset, or what ctf_set_state handed in / the env folded) plus 1 at the logged cell of
+ * every step since; N * G * G = ctf_visitation_words(env) true counts [N][G * G], nothing wraps at 256 (callers that want the
+ * reference's uint8 maps take `& 0xFF`: its `+=` on uint8 arrays wraps, and the sum of wrapped counts is congruent to the wrapped
+ * sum of true counts).  Both calls fail with CTF_E_INVALID on a handle created with log_metrics == 0 (it keeps no maps); both are one
+ * kernel launch and nothing else (stream-ordered, no allocation, no synchronisation, capturable behind ctf_step_observe); env state
+ * is only read.
+ * ctf_harvest_visitation: the per-group form.  acc_dev is a caller-owned table int64 [n_groups][N][G * G], 8-byte aligned, that the
+ *   call ADDS to.  It takes the same envs under the same rules as ctf_harvest_episodes (`done` set and env_step_count ==
+ *   GAME_STEPS, or every env with CTF_HARVEST_ALL; group_dev, NULL = group 0; env_mask_dev; an id outside [0, n_groups) skips the
+ *   env and raises CTF_ST_BAD_GROUP): a call behind the same step with the same arguments covers exactly the same episodes, so row
+ *   g sums to N * (steps + episodes) of the episode harvest's row g.  Integer sums: the table does not depend on the order of additions.
+ * ctf_export_visitation: the per-env form.  out_dev[k] = the map of env idx_dev[k], uint32 [n][N][G * G], k < n; idx_dev NULL = envs
+ *   0..n-1 (n <= E).  Repeats allowed.  An index outside [0, E) writes nothing for that record and raises CTF_ST_BAD_GROUP (the
+ *   bit of "an id named no row of this handle": no new bit is needed). */
+int32_t ctf_visitation_words(const ctf_env* env); /* N * G * G; 0 for a null handle */
+int ctf_harvest_visitation(ctf_env* env, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
+                           int64_t* acc_dev, void* stream);
+int ctf_export_visitation(ctf_env* env, const int32_t* idx_dev, int32_t n, uint32_t* out_dev, void* stream);
 
 /* Sticky status bits raised by any env since the last call (synchronises `stream`, clears them). */
 int ctf_status(ctf_env* env, uint32_t* out_bits, void* stream);

@@ -145,6 +145,9 @@ SYMBOLS = {
     "ctf_load_states": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ctf_harvest_words": (C.c_int32, [_P]),
     "ctf_harvest_episodes": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P]),
+    "ctf_visitation_words": (C.c_int32, [_P]),
+    "ctf_harvest_visitation": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P]),
+    "ctf_export_visitation": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "ctf_export_counters": (C.c_int, [_P, _P, _P, _P, _P]),
     "ctf_status": (C.c_int, [_P, C.POINTER(C.c_uint32), _P]),
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),

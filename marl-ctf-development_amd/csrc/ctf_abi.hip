@@ -20,6 +20,7 @@
 #include "ctf_harvest.h"
 #include "ctf_launch.h"
 #include "ctf_snapshot.h"
+#include "ctf_visitation.h"
 
 struct ctf_env {
     ctf_config cfg;
@@ -676,6 +677,34 @@ extern "C" int ctf_harvest_episodes(ctf_env* h, const int32_t* group_dev, int32_
     if (flags & ~CTF_HARVEST_ALL) return fail(CTF_E_INVALID, "ctf_harvest_episodes: unknown flags 0x%x", flags);
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_harvest(harvest_args(h->d, h->p), group_dev, n_groups, env_mask_dev, flags, acc_dev, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+// ---- visitation maps (ctf_visitation.h / ctf_visitation.hip) --------------------------------------------------------------------
+extern "C" int32_t ctf_visitation_words(const ctf_env* h) { return h ? visitation_words(h->d) : 0; }
+
+extern "C" int ctf_harvest_visitation(ctf_env* h, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
+                                      int64_t* acc_dev, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_harvest_visitation: null handle");
+    if (!h->d.log_metrics) return fail(CTF_E_INVALID, "ctf_harvest_visitation: the handle keeps no visitation maps (log_metrics == 0)");
+    if (n_groups < 1) return fail(CTF_E_INVALID, "ctf_harvest_visitation: n_groups = %d", n_groups);
+    if (!acc_dev) return fail(CTF_E_INVALID, "ctf_harvest_visitation: null table");
+    if ((uintptr_t)acc_dev % 8) return fail(CTF_E_INVALID, "ctf_harvest_visitation: the table must be 8-byte aligned");
+    if (flags & ~CTF_HARVEST_ALL) return fail(CTF_E_INVALID, "ctf_harvest_visitation: unknown flags 0x%x", flags);
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_visit_harvest(visit_args(h->d, h->p), group_dev, n_groups, env_mask_dev, flags, acc_dev, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+extern "C" int ctf_export_visitation(ctf_env* h, const int32_t* idx_dev, int32_t n, uint32_t* out_dev, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_export_visitation: null handle");
+    if (!h->d.log_metrics) return fail(CTF_E_INVALID, "ctf_export_visitation: the handle keeps no visitation maps (log_metrics == 0)");
+    if (n < 0) return fail(CTF_E_INVALID, "ctf_export_visitation: n = %d", n);
+    if (!idx_dev && n > h->d.n_envs) return fail(CTF_E_INVALID, "ctf_export_visitation: n = %d > %d envs", n, h->d.n_envs);
+    if (!out_dev && n > 0) return fail(CTF_E_INVALID, "ctf_export_visitation: null output");
+    if ((uintptr_t)out_dev % 4) return fail(CTF_E_INVALID, "ctf_export_visitation: the output must be 4-byte aligned");
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_visit_export(visit_args(h->d, h->p), idx_dev, n, out_dev, (hipStream_t)stream));
     return CTF_OK;
 }
 

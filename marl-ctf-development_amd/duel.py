@@ -5,7 +5,8 @@ team-0 agents are driven by ``agent`` and team-1 agents by ``opponent`` whose ac
 ``REVERSED_ACTION_MAP`` (utils.py:535-551); the loop ends when the env reports ``done`` or after ``max_steps + 1``
 steps (``step_count > max_steps``, utils.py:559).  All envs of a batch share GAME_STEPS and start together, so they
 all stop at the same step.  Returns what the reference returns per env: the result sign (utils.py:562-569) and the
-counters ``env.metrics`` holds (as tensors; ``VecGridworldCtf.counters``).
+counters ``env.metrics`` holds (as tensors; ``VecGridworldCtf.counters``) and, with ``visitation=True``, its visitation maps
+(``metrics['agent_visitation_maps']``, what ``utils.plot_heatmaps`` sums over its duels; utils.py:263-400) as true counts.
 """
 import numpy as np
 
@@ -17,9 +18,12 @@ except ImportError:  # pragma: no cover
     from rollout import BatchedRolloutCollector
 
 
-def batched_duel(vec, agent, opponent, max_steps=256):
+def batched_duel(vec, agent, opponent, max_steps=256, visitation=False):
     """-> dict(result int8 [E] (+1 team 0 wins, 0 draw, -1 team 1 wins), team_flag_captures int32 [E, 2],
-    metrics int32 [E, 13, N], steps int)."""
+    metrics int32 [E, 13, N], steps int).  ``visitation=True`` adds ``visitation``, uint32 [E, N, G, G]: every env's maps at the
+    end of its duel as true counts (one ``VecGridworldCtf.visitation`` launch).  ``(sum over envs) & 0xFF`` as uint8 is what
+    ``utils.plot_heatmaps`` returns for the same duels: its ``+=`` on uint8 arrays wraps, and the sum of wrapped counts is
+    congruent mod 256 to the wrapped sum of true counts."""
     import torch
 
     col = BatchedRolloutCollector(vec, 1, 0)  # reuses the policy plumbing; its rollout buffers hold one step
@@ -32,17 +36,22 @@ def batched_duel(vec, agent, opponent, max_steps=256):
             vec.step(col.joint_actions(agent, opponent, use_codes)[1])
     metrics, caps, _ = vec.counters()
     result = torch.sign(caps[:, 0] - caps[:, 1]).to(torch.int8)
-    return dict(result=result, team_flag_captures=caps, metrics=metrics, steps=n_steps)
+    out = dict(result=result, team_flag_captures=caps, metrics=metrics, steps=n_steps)
+    if visitation:
+        out["visitation"] = vec.visitation()
+    return out
 
 
-def batched_tournament(vec, agents, opponents, max_steps=256):
+def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
     """Every pairing of ``agents`` (team 0) with ``opponents`` (team 1) in ONE batch: the batched form of the league's pairing
     loops (reference league_training.py:573-648).  The E envs are cut into ``len(agents) * len(opponents)`` contiguous, equal
     blocks, agent-major: block (a, b) — group ``a * len(opponents) + b`` — plays ``agents[a]`` against ``opponents[b]``, each env
     one duel as ``batched_duel`` plays it.  Every policy is called once per step, through ``get_action_and_value(grid, metadata,
     mask)``, on the rows of the envs it plays in.  One harvest after the last step gives the table.
     -> dict(episodes int64 [A, B], result_counts int64 [A, B, 3] (team 0 wins, draws, team 1 wins), win_rate float64 [A, B]
-    (team 0's), table int64 [A * B, H] (``harvest.EpisodeHarvest``: ``results(g, table)`` / ``metrics(g, table)``), steps)."""
+    (team 0's), table int64 [A * B, H] (``harvest.EpisodeHarvest``: ``results(g, table)`` / ``metrics(g, table)``), steps).  ``visitation=True`` adds ``visitation``,
+    int64 numpy [A, B, N, G, G]: each pairing's visitation maps summed over its envs, true counts, from one
+    ``harvest_visitation(all_envs=True)`` beside the harvest."""
     import torch
 
     A, B, E = len(agents), len(opponents), vec.n_envs
@@ -52,7 +61,7 @@ def batched_tournament(vec, agents, opponents, max_steps=256):
     col = BatchedRolloutCollector(vec, 1, 0)  # the policy plumbing of batched_duel
     dev = vec.device
     env = torch.arange(E, device=dev)
-    harvest = EpisodeHarvest(vec, A * B, env // per)
+    harvest = EpisodeHarvest(vec, A * B, env // per, visitation=True) if visitation else EpisodeHarvest(vec, A * B, env // per)
     # rows of opponent b: its block under every agent
     rows_of = [torch.cat([env[(a * B + b) * per:(a * B + b + 1) * per] for a in range(A)]) for b in range(B)]
     acts = torch.zeros((E, vec.N_AGENTS), dtype=torch.int8, device=dev)
@@ -74,7 +83,10 @@ def batched_tournament(vec, agents, opponents, max_steps=256):
     table = harvest.table()
     episodes = table[:, 0].reshape(A, B)
     counts = table[:, 1:4].reshape(A, B, 3)
-    return dict(episodes=episodes, result_counts=counts, win_rate=counts[:, :, 0] / np.maximum(episodes, 1), table=table, steps=n_steps)
+    out = dict(episodes=episodes, result_counts=counts, win_rate=counts[:, :, 0] / np.maximum(episodes, 1), table=table, steps=n_steps)
+    if visitation:
+        out["visitation"] = harvest.visitation_table().reshape(A, B, vec.N_AGENTS, vec.GRID_SIZE, vec.GRID_SIZE)
+    return out
 
 
 def duel_trajectory(vec, agent, opponent, env_index=0, max_steps=256):

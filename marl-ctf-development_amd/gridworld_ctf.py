@@ -496,6 +496,48 @@ class VecGridworldCtf:
         self._call("ctf_harvest_episodes", g, int(acc.shape[0]), m, _abi.HARVEST_ALL if all_envs else 0, _abi.ptr(acc), self._stream())
         return acc
 
+    # -- visitation maps in bulk (include/ctf_env.h, ctf_harvest_visitation / ctf_export_visitation) --------------------------
+    @property
+    def visitation_words(self):
+        """N * G * G: words of one env's (or one group's) visitation maps."""
+        return int(self._lib.ctf_visitation_words(self._h))
+
+    def harvest_visitation(self, acc, groups=None, mask=None, all_envs=False):
+        """ADD the visitation maps (true counts: no u8 wrap) of the envs ``harvest`` takes under the same arguments into ``acc``,
+        int64 [n_groups, N, G, G] on the envs' device.  One stream-ordered launch; behind the same step it covers exactly the
+        episodes ``harvest`` covers.  Needs ``log_metrics=True``."""
+        torch = _torch()
+        N, G = self.N_AGENTS, self.GRID_SIZE
+        if not (isinstance(acc, torch.Tensor) and acc.dtype == torch.int64 and acc.is_cuda and acc.device == self.device):
+            raise ValueError(f"harvest_visitation: expected an int64 table on {self.device}")
+        if acc.dim() != 4 or acc.shape[0] < 1 or tuple(acc.shape[1:]) != (N, G, G) or not acc.is_contiguous():
+            raise ValueError(f"harvest_visitation: expected a contiguous table of shape [n_groups >= 1, {N}, {G}, {G}], got {list(acc.shape)}")
+        if not self.cfg.log_metrics:
+            raise ValueError("harvest_visitation: the envs keep no visitation maps (log_metrics=False)")
+        g = None if groups is None else self._check_dev(groups, torch.int32, self.n_envs)
+        m = None if mask is None else self._check_dev(mask, torch.uint8, self.n_envs)
+        self._call("ctf_harvest_visitation", g, int(acc.shape[0]), m, _abi.HARVEST_ALL if all_envs else 0, _abi.ptr(acc), self._stream())
+        return acc
+
+    def visitation(self, idx=None, out=None):
+        """Visitation maps of envs ``idx`` (None: all) -> uint32 [n, N, G, G] on the envs' device (``out`` if given): true counts,
+        ``& 0xFF`` is ``metrics['agent_visitation_maps']``.  One stream-ordered launch, repeats allowed.  Host index lists are
+        range-checked here; a device list is not (no synchronisation): an index outside [0, n_envs) leaves its record unwritten and
+        ``status()`` shows ST_BAD_GROUP."""
+        torch = _torch()
+        N, G = self.N_AGENTS, self.GRID_SIZE
+        if not self.cfg.log_metrics:
+            raise ValueError("visitation: the envs keep no visitation maps (log_metrics=False)")
+        ix, n = self._index_list(idx, "visitation", check=False)
+        if out is None:
+            out = torch.empty((n, N, G, G), dtype=torch.uint32, device=self.device)
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint32 and out.is_cuda and out.device == self.device):
+            raise ValueError(f"visitation: expected a uint32 output on {self.device}")
+        if tuple(out.shape) != (n, N, G, G) or not out.is_contiguous():
+            raise ValueError(f"visitation: expected a contiguous output of shape [{n}, {N}, {G}, {G}], got {list(out.shape)}")
+        self._call("ctf_export_visitation", _abi.ptr(ix), n, _abi.ptr(out), self._stream())
+        return out
+
     # -- host views ---------------------------------------------------------------------------
     def get_state(self, env_index):
         v = _abi.CtfStateView()

@@ -13,7 +13,13 @@ kernel launch, ``ctf_harvest_episodes`` — adds the envs whose episode ended in
 
 ``results`` is the batched form of ``utils.duel(..., return_result=True)`` (reference utils.py:562-569), ``metrics`` of the
 ``env.metrics`` entries ``MetricsLogger.harvest_metrics`` reads (metrics_logger.py:137-159) — both as SUMS over the group's
-harvested episodes: divide by ``episodes`` or pass a scaling factor.  Visitation maps are not harvested.
+harvested episodes: divide by ``episodes`` or pass a scaling factor.
+
+The visitation maps (``metrics['agent_visitation_maps']``, what the reference's ``utils.plot_heatmaps`` sums over its duels) are
+harvested too when asked for: ``EpisodeHarvest(vec, n_groups, groups, visitation=True)`` owns a second table, ``vis_acc`` int64
+[n_groups, N, G, G], ``update()`` then issues a second launch (``ctf_harvest_visitation``) with the same arguments, which takes
+exactly the same envs, and ``visitation(g)`` gives the group's maps as TRUE counts summed over its episodes (the reference's
+uint8 maps are these ``& 0xFF``).  Across GPUs the table is small: ``all_reduce(h.vis_acc)`` is the whole reduction.
 """
 import numpy as np
 
@@ -29,9 +35,9 @@ EPISODES, WINS, DRAWS, LOSSES, CAPTURES_0, CAPTURES_1, STEPS = range(7)
 
 
 class EpisodeHarvest:
-    def __init__(self, vec, n_groups=1, groups=None):
+    def __init__(self, vec, n_groups=1, groups=None, visitation=False):
         """vec: VecGridworldCtf.  groups: the group of every env (int tensor / array [E], values in [0, n_groups)), None =
-        every env is group 0."""
+        every env is group 0.  visitation: also harvest the visitation maps, into ``vis_acc`` int64 [n_groups, N, G, G]."""
         import torch
 
         self.vec = vec
@@ -50,18 +56,45 @@ class EpisodeHarvest:
             if g.numel() and (int(g.min()) < 0 or int(g.max()) >= self.n_groups):
                 raise ValueError(f"groups: an id is outside [0, {self.n_groups})")
             self.groups = g.to(device=vec.device, dtype=torch.int32).contiguous()
+        self.vis_acc = None
+        if visitation:
+            n, gsz = int(vec.N_AGENTS), int(vec.GRID_SIZE)
+            if int(vec.visitation_words) != n * gsz * gsz:
+                raise ValueError("visitation_words does not match N * G * G of this binding")
+            self.vis_acc = torch.zeros((self.n_groups, n, gsz, gsz), dtype=torch.int64, device=vec.device)
 
     def update(self, mask=None, all_envs=False):
         """Add the envs whose episode ended in the most recent step (``all_envs``: every env as it stands — the cut of a
-        truncated duel); ``mask`` uint8 [E]: only envs whose byte is non-zero.  One launch, stream-ordered."""
+        truncated duel); ``mask`` uint8 [E]: only envs whose byte is non-zero.  One launch, stream-ordered (with
+        ``visitation=True`` a second one, with the same arguments: the same envs)."""
         self.vec.harvest(self.acc, groups=self.groups, mask=mask, all_envs=all_envs)
+        if self.vis_acc is not None:
+            self.vec.harvest_visitation(self.vis_acc, groups=self.groups, mask=mask, all_envs=all_envs)
 
     def zero(self):
         self.acc.zero_()
+        if self.vis_acc is not None:
+            self.vis_acc.zero_()
 
     def table(self):
         """-> int64 numpy [n_groups, H]: one device-to-host copy."""
         return self.acc.cpu().numpy()
+
+    def visitation_table(self):
+        """-> int64 numpy [n_groups, N, G, G]: one device-to-host copy (``visitation=True`` only)."""
+        if self.vis_acc is None:
+            raise ValueError("this harvest was built without visitation=True")
+        return self.vis_acc.cpu().numpy()
+
+    def visitation(self, g, table=None):
+        """-> {agent: int64 [G, G]}: the shape of the reference's ``metrics['agent_visitation_maps']``, summed over group g's
+        harvested episodes WITHOUT the reference's uint8 wrap (``& 0xFF`` gives its maps)::
+
+            m = h.metrics(g); m["agent_visitation_maps"] = h.visitation(g)
+
+        ``table``: a copy taken earlier with ``visitation_table()``."""
+        maps = np.asarray((self.visitation_table() if table is None else table)[g])
+        return {i: maps[i].astype(np.int64) for i in range(maps.shape[0])}
 
     def results(self, g, table=None):
         """-> dict(episodes, wins, draws, losses (team 0's point of view), team_flag_captures {team: sum}, mean_steps) of group g.
