@@ -13,8 +13,8 @@
  *     the library never allocates or frees I/O buffers;
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
- *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation and
- *     ctf_export_visitation are kernel launches and nothing else (no
+ *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
+ *     ctf_export_visitation, ctf_export_states and ctf_import_states are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -58,6 +58,9 @@ extern "C" {
                                    (ctf_save_states: a source index outside [0, E); that record's header is left invalid)      */
 #define CTF_ST_BAD_GROUP 64u    /* ctf_harvest_episodes / ctf_harvest_visitation: a group id outside [0, n_groups); that env is skipped
                                    (ctf_export_visitation: an env index outside [0, E); that record is not written)             */
+
+#define CTF_ST_BAD_STATE 128u   /* ctf_import_states: a record broke one of ctf_set_state's rules, or its index was outside [0, E);
+                                   that env is untouched */
 
 /* ctf_config.rng_mode */
 #define CTF_RNG_MT19937 0 /* the reference's two MT19937 generators, bit for bit (default)                          */
@@ -352,6 +355,38 @@ int32_t ctf_visitation_words(const ctf_env* env); /* N * G * G; 0 for a null han
 int ctf_harvest_visitation(ctf_env* env, const int32_t* group_dev, int32_t n_groups, const uint8_t* env_mask_dev, uint32_t flags,
                            int64_t* acc_dev, void* stream);
 int ctf_export_visitation(ctf_env* env, const int32_t* idx_dev, int32_t n, uint32_t* out_dev, void* stream);
+
+/* Env states as plain arrays, in bulk and on the device: ctf_get_state / ctf_set_state for many envs in ONE stream-ordered kernel
+ * launch each (no allocation, no copy, no synchronisation: capturable behind ctf_step_observe), without the host decode.
+ * ctf_state_arrays holds DEVICE pointers.  Every member may be NULL (export: not wanted; import: see below), every pointer is
+ * 16-byte aligned, and record k's row is dense: [n][...] with no padding to the device form's strides. */
+typedef struct ctf_state_arrays {
+    uint8_t* grid;          /* u8  [n][G*G]    self.grid, row-major                          */
+    int8_t*  pos;           /* i8  [n][N][2]   agent_positions (row, col)                    */
+    double*  hp;            /* f64 [n][N]                                                    */
+    uint8_t* has_flag;      /* u8  [n][N]                                                    */
+    int32_t* inventory;     /* i32 [n][N]      block_inventory (as ctf_state_view)           */
+    uint8_t* perm;          /* u8  [n][N]      _arr                                          */
+    int32_t* step_count;    /* i32 [n]                                                       */
+    int32_t* team_captures; /* i32 [n][2]                                                    */
+    uint8_t* done;          /* u8  [n]                                                       */
+    int32_t* metrics;       /* i32 [n][13][N]  CTF_M_* order                                 */
+    uint8_t* visitation;    /* IMPORT ONLY: u8 [n][N][G*G] base maps (ctf_set_state's)       */
+} ctf_state_arrays;
+/* ctf_export_states: record k of every non-NULL array = what ctf_get_state of env idx_dev[k] would show, bit for bit (hp too).
+ *   idx_dev NULL = envs 0..n-1 (n <= E).  Repeats allowed.  An index outside [0, E) writes nothing for that record in any array
+ *   and raises CTF_ST_BAD_GROUP (ctf_export_visitation's rule).  out->visitation must be NULL (ctf_export_visitation is the export
+ *   of the maps) and out->metrics must be NULL on a handle with log_metrics == 0: CTF_E_INVALID.  Env state is only read.
+ * ctf_import_states: ctf_set_state for many envs — env idx_dev[k] := record k, k < n <= E; idx_dev NULL = envs 0..n-1.  Indices must
+ *   be distinct (repeats: undefined).  grid, pos, hp, has_flag, inventory, perm, step_count, team_captures and done are required
+ *   (CTF_E_INVALID).  metrics NULL = zeros.  visitation NULL = the maps restart as after reset() (+1 at the config's start cells);
+ *   non-NULL = the given u8 maps become the base maps.  Either way the visitation log is empty (folded up to step_count), exactly
+ *   as ctf_set_state leaves it.  Either optional array on a log_metrics == 0 handle: CTF_E_INVALID.  The kernel applies
+ *   ctf_set_state's checks per record — pos inside the grid, perm[i] < N, inventory in 0..1000, grid codes <= 13, 0 <= step_count
+ *   < 2^28, index in [0, E) — and a record that fails writes NOTHING for that env and raises CTF_ST_BAD_STATE.  An env set by
+ *   either call holds the same device bytes.  The generators are not touched; observations are not state. */
+int ctf_export_states(ctf_env* env, const int32_t* idx_dev, int32_t n, const ctf_state_arrays* out, void* stream);
+int ctf_import_states(ctf_env* env, const ctf_state_arrays* in, const int32_t* idx_dev, int32_t n, void* stream);
 
 /* Sticky status bits raised by any env since the last call (synchronises `stream`, clears them). */
 int ctf_status(ctf_env* env, uint32_t* out_bits, void* stream);

@@ -22,6 +22,7 @@ ST_RNG_OVERRUN = 8
 ST_SYNC_TIMEOUT = 16
 ST_BAD_SNAPSHOT = 32
 ST_BAD_GROUP = 64
+ST_BAD_STATE = 128
 STEP_AUTO_RESET = 1
 HARVEST_ALL = 1
 HARVEST_HEAD = 8  # words of a harvest row before the counters (include/ctf_env.h, ctf_harvest_episodes)
@@ -103,6 +104,14 @@ class CtfStateView(C.Structure):
     ]
 
 
+# members of ctf_state_arrays in the struct's order (device pointers); "visitation" is import-only
+STATE_FIELDS = ("grid", "pos", "hp", "has_flag", "inventory", "perm", "step_count", "team_captures", "done", "metrics", "visitation")
+
+
+class CtfStateArrays(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in STATE_FIELDS]
+
+
 class CtfLibraryError(RuntimeError):
     pass
 
@@ -149,6 +158,8 @@ SYMBOLS = {
     "ctf_harvest_visitation": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P, _P]),
     "ctf_export_visitation": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "ctf_export_counters": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ctf_export_states": (C.c_int, [_P, _P, C.c_int32, C.POINTER(CtfStateArrays), _P]),
+    "ctf_import_states": (C.c_int, [_P, C.POINTER(CtfStateArrays), _P, C.c_int32, _P]),
     "ctf_status": (C.c_int, [_P, C.POINTER(C.c_uint32), _P]),
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),

@@ -20,6 +20,7 @@
 #include "ctf_harvest.h"
 #include "ctf_launch.h"
 #include "ctf_snapshot.h"
+#include "ctf_states.h"
 #include "ctf_visitation.h"
 
 struct ctf_env {
@@ -705,6 +706,43 @@ extern "C" int ctf_export_visitation(ctf_env* h, const int32_t* idx_dev, int32_t
     if ((uintptr_t)out_dev % 4) return fail(CTF_E_INVALID, "ctf_export_visitation: the output must be 4-byte aligned");
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_visit_export(visit_args(h->d, h->p), idx_dev, n, out_dev, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+// ---- env states as plain arrays (ctf_states.h / ctf_states.hip) -------------------------------------------------------------------
+static const char* const k_state_names[ST_FIELDS] = {"grid", "pos", "hp", "has_flag", "inventory", "perm", "step_count", "team_captures", "done",
+                                                     "metrics", "visitation"};
+static int state_args(const ctf_env* h, const ctf_state_arrays* a, int32_t n, bool have_idx, const char* what, StateArrays* out) {
+    if (!h || !a) return fail(CTF_E_INVALID, "%s: null argument", what);
+    if (n < 0) return fail(CTF_E_INVALID, "%s: n = %d", what, n);
+    if (!have_idx && n > h->d.n_envs) return fail(CTF_E_INVALID, "%s: n = %d > %d envs", what, n, h->d.n_envs);
+    uint8_t* const ptrs[ST_FIELDS] = {a->grid, (uint8_t*)a->pos, (uint8_t*)a->hp, a->has_flag, (uint8_t*)a->inventory, a->perm, (uint8_t*)a->step_count,
+                                      (uint8_t*)a->team_captures, a->done, (uint8_t*)a->metrics, a->visitation};
+    for (int f = 0; f < ST_FIELDS; f++) {
+        if ((uintptr_t)ptrs[f] % 16) return fail(CTF_E_INVALID, "%s: %s must be 16-byte aligned", what, k_state_names[f]);
+        out->arr[f] = ptrs[f];
+    }
+    if (a->metrics && !h->d.log_metrics) return fail(CTF_E_INVALID, "%s: metrics on a handle that keeps no counters (log_metrics == 0)", what);
+    return CTF_OK;
+}
+
+extern "C" int ctf_export_states(ctf_env* h, const int32_t* idx_dev, int32_t n, const ctf_state_arrays* out, void* stream) {
+    StateArrays A;
+    if (int rc = state_args(h, out, n, idx_dev != nullptr, "ctf_export_states", &A)) return rc;
+    if (out->visitation) return fail(CTF_E_INVALID, "ctf_export_states: visitation must be NULL (ctf_export_visitation exports the maps)");
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_export_states(state_shape(h->d), state_dev(h->d, h->p), idx_dev, n, A, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+extern "C" int ctf_import_states(ctf_env* h, const ctf_state_arrays* in, const int32_t* idx_dev, int32_t n, void* stream) {
+    StateArrays A;
+    if (int rc = state_args(h, in, n, false, "ctf_import_states", &A)) return rc;
+    for (int f = 0; f < ST_METRICS; f++)
+        if (!A.arr[f]) return fail(CTF_E_INVALID, "ctf_import_states: %s is required", k_state_names[f]);
+    if (in->visitation && !h->d.log_metrics) return fail(CTF_E_INVALID, "ctf_import_states: visitation on a handle that keeps no maps (log_metrics == 0)");
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_import_states(state_shape(h->d), state_dev(h->d, h->p), A, idx_dev, n, (hipStream_t)stream));
     return CTF_OK;
 }
 

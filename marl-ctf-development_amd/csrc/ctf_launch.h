@@ -1,5 +1,5 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip and ctf_visitation.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip and ctf_states.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include "ctf_device.h"
 #include "ctf_harvest.h"
 #include "ctf_snapshot.h"
+#include "ctf_states.h"
 #include "ctf_visitation.h"
 
 // what one step reads and writes (ctf_step's arguments)
@@ -56,4 +57,7 @@ hipError_t ctf_launch_harvest(const HarvestArgs&, const int32_t* group, int n_gr
 // ---- ctf_visitation.hip
 hipError_t ctf_launch_visit_harvest(const VisitArgs&, const int32_t* group, int n_groups, const uint8_t* mask, uint32_t flags, int64_t* acc, hipStream_t);
 hipError_t ctf_launch_visit_export(const VisitArgs&, const int32_t* idx, int n, uint32_t* out, hipStream_t);
+// ---- ctf_states.hip
+hipError_t ctf_launch_export_states(const StateShape&, const StateDev&, const int32_t* idx, int n, const StateArrays& out, hipStream_t);
+hipError_t ctf_launch_import_states(const StateShape&, const StateDev&, const StateArrays& in, const int32_t* idx, int n, hipStream_t);
 }

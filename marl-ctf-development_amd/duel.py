@@ -11,9 +11,11 @@ counters ``env.metrics`` holds (as tensors; ``VecGridworldCtf.counters``) and, w
 import numpy as np
 
 try:
+    from .frames import StateRecorder, frames_to_trajectory
     from .harvest import EpisodeHarvest
     from .rollout import BatchedRolloutCollector
 except ImportError:  # pragma: no cover
+    from frames import StateRecorder, frames_to_trajectory
     from harvest import EpisodeHarvest
     from rollout import BatchedRolloutCollector
 
@@ -42,7 +44,7 @@ def batched_duel(vec, agent, opponent, max_steps=256, visitation=False):
     return out
 
 
-def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
+def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False, record=None):
     """Every pairing of ``agents`` (team 0) with ``opponents`` (team 1) in ONE batch: the batched form of the league's pairing
     loops (reference league_training.py:573-648).  The E envs are cut into ``len(agents) * len(opponents)`` contiguous, equal
     blocks, agent-major: block (a, b) — group ``a * len(opponents) + b`` — plays ``agents[a]`` against ``opponents[b]``, each env
@@ -51,7 +53,9 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
     -> dict(episodes int64 [A, B], result_counts int64 [A, B, 3] (team 0 wins, draws, team 1 wins), win_rate float64 [A, B]
     (team 0's), table int64 [A * B, H] (``harvest.EpisodeHarvest``: ``results(g, table)`` / ``metrics(g, table)``), steps).  ``visitation=True`` adds ``visitation``,
     int64 numpy [A, B, N, G, G]: each pairing's visitation maps summed over its envs, true counts, from one
-    ``harvest_visitation(all_envs=True)`` beside the harvest."""
+    ``harvest_visitation(all_envs=True)`` beside the harvest.  ``record=k`` records the first k envs of every pairing's block (one
+    ``frames.StateRecorder`` launch per step) and adds ``trajectories``, [A][B][k] dicts as ``duel_trajectory`` builds them; the
+    default makes no recorder, no key and no launch."""
     import torch
 
     A, B, E = len(agents), len(opponents), vec.n_envs
@@ -66,7 +70,15 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
     rows_of = [torch.cat([env[(a * B + b) * per:(a * B + b + 1) * per] for a in range(A)]) for b in range(B)]
     acts = torch.zeros((E, vec.N_AGENTS), dtype=torch.int8, device=dev)
     n_steps = min(int(vec.cfg.game_steps), int(max_steps) + 1)
+    recorder = None
+    if record is not None:
+        k = int(record)
+        if k < 1 or k > per:
+            raise ValueError(f"record = {record}: a pairing's block has {per} envs")
+        recorder = StateRecorder(vec, [g * per + j for g in range(A * B) for j in range(k)], n_steps + 1)
     vec.reset()
+    if recorder:
+        recorder.record()
     with torch.no_grad():
         for _ in range(n_steps):
             obs, meta = vec.observe()
@@ -79,6 +91,8 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
                 acts[rows[:, None], col.others_idx[None, :]] = act.to(torch.int8).transpose(0, 1)
             mapped = col.rev_lut[acts.long()]  # team-1 agents act in their flipped view (utils.py:535-551)
             vec.step(torch.where(col.is_team1[None, :], mapped, acts).contiguous())
+            if recorder:
+                recorder.record()
     harvest.update(all_envs=True)
     table = harvest.table()
     episodes = table[:, 0].reshape(A, B)
@@ -86,6 +100,9 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False):
     out = dict(episodes=episodes, result_counts=counts, win_rate=counts[:, :, 0] / np.maximum(episodes, 1), table=table, steps=n_steps)
     if visitation:
         out["visitation"] = harvest.visitation_table().reshape(A, B, vec.N_AGENTS, vec.GRID_SIZE, vec.GRID_SIZE)
+    if recorder:
+        fr = recorder.frames()
+        out["trajectories"] = [[[frames_to_trajectory(vec, fr, (a * B + b) * k + j) for j in range(k)] for b in range(B)] for a in range(A)]
     return out
 
 
@@ -134,3 +151,23 @@ def duel_trajectory(vec, agent, opponent, env_index=0, max_steps=256):
             pos = new_pos
     out["movement"], out["tiles"], out["scores"] = movement, tiles, scores
     return out
+
+
+def duel_trajectories(vec, agent, opponent, env_indices, max_steps=256):
+    """``duel_trajectory`` for SEVERAL envs of one batched duel: the envs' states are recorded on the device, one
+    ``frames.StateRecorder`` launch per step instead of one ``get_state`` round trip per env and step, and decoded on the host after
+    the last step.  -> a list of dicts, entry j the record of env ``env_indices[j]`` (repeats allowed)."""
+    import torch
+
+    col = BatchedRolloutCollector(vec, 1, 0)
+    use_codes = col.use_codes(agent, opponent)
+    n_steps = min(int(vec.cfg.game_steps), int(max_steps) + 1)
+    recorder = StateRecorder(vec, env_indices, n_steps + 1)
+    vec.reset()
+    recorder.record()
+    with torch.no_grad():
+        for _ in range(n_steps):
+            vec.step(col.joint_actions(agent, opponent, use_codes)[1])
+            recorder.record()
+    fr = recorder.frames()
+    return [frames_to_trajectory(vec, fr, j) for j in range(recorder.n)]

@@ -538,6 +538,96 @@ class VecGridworldCtf:
         self._call("ctf_export_visitation", _abi.ptr(ix), n, _abi.ptr(out), self._stream())
         return out
 
+    # -- env states as plain arrays, in bulk (include/ctf_env.h, ctf_export_states / ctf_import_states) -----------------------------
+    def _state_specs(self):
+        """name -> (dtype, shape of one record) of every member of ctf_state_arrays"""
+        torch = _torch()
+        N, G = self.N_AGENTS, self.GRID_SIZE
+        return dict(grid=(torch.uint8, (G, G)), pos=(torch.int8, (N, 2)), hp=(torch.float64, (N,)), has_flag=(torch.uint8, (N,)),
+                    inventory=(torch.int32, (N,)), perm=(torch.uint8, (N,)), step_count=(torch.int32, ()),
+                    team_captures=(torch.int32, (2,)), done=(torch.uint8, ()), metrics=(torch.int32, (_abi.N_METRICS, N)),
+                    visitation=(torch.uint8, (N, G, G)))
+
+    def _state_arrays(self, tensors, n, what):
+        """dict name -> tensor, validated against the specs -> the struct of device pointers"""
+        torch = _torch()
+        specs = self._state_specs()
+        arrs = _abi.CtfStateArrays()
+        for name, t in tensors.items():
+            dtype, tail = specs[name]
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dtype):
+                raise ValueError(f"{what}: {name} must be a {dtype} tensor on {self.device}")
+            if tuple(t.shape) != (n,) + tail:
+                raise ValueError(f"{what}: {name} must have shape {[n] + list(tail)}, got {list(t.shape)}")
+            if not t.is_contiguous() or t.data_ptr() % 16:
+                raise ValueError(f"{what}: {name} must be contiguous and 16-byte aligned")
+            setattr(arrs, name, t.data_ptr())
+        return arrs
+
+    def get_states(self, idx=None, fields=None, out=None):
+        """The readable state of envs ``idx`` (None: all) as a dict of tensors on the envs' device, record k = what ``get_state(idx[k])``
+        shows, bit for bit: grid uint8 [n, G, G], pos int8 [n, N, 2], hp float64 [n, N], has_flag uint8 [n, N], inventory int32 [n, N],
+        perm uint8 [n, N], step_count int32 [n], team_captures int32 [n, 2], done uint8 [n] and, with ``log_metrics``, metrics int32
+        [n, 13, N].  ``fields`` selects a subset (only those are written); ``out`` is a dict to reuse: its tensors of the selected
+        names are written in place, missing ones are allocated and added.  One stream-ordered launch, repeats allowed.  Host index
+        lists are range-checked here; a device list is not (no synchronisation): an index outside [0, n_envs) leaves its record
+        unwritten and ``status()`` shows ST_BAD_GROUP.  The visitation maps have their own export, ``visitation()``."""
+        torch = _torch()
+        specs = self._state_specs()
+        exportable = [f for f in _abi.STATE_FIELDS[:-1] if f != "metrics" or self.cfg.log_metrics]
+        names = exportable if fields is None else list(fields)
+        for f in names:
+            if f == "visitation":
+                raise ValueError("get_states: the visitation maps are exported by visitation()")
+            if f not in specs:
+                raise ValueError(f"get_states: unknown field {f!r}")
+            if f == "metrics" and not self.cfg.log_metrics:
+                raise ValueError("get_states: the envs keep no counters (log_metrics=False)")
+        ix, n = self._index_list(idx, "get_states", check=False)
+        out = {} if out is None else out
+        for f in names:
+            if f not in out:
+                out[f] = torch.empty((n,) + specs[f][1], dtype=specs[f][0], device=self.device)
+        arrs = self._state_arrays({f: out[f] for f in names}, n, "get_states")
+        if n and names:
+            self._call("ctf_export_states", _abi.ptr(ix), n, C.byref(arrs), self._stream())
+        return out
+
+    def set_states(self, states, idx=None, check=True):
+        """Env ``idx[k]`` := record k of ``states`` (idx None: envs 0..n-1): ``set_state`` for many envs in one stream-ordered launch.
+        ``states`` is a dict as ``get_states`` returns it; every field but ``metrics`` (missing: zeros) and ``visitation`` (uint8 [n, N,
+        G, G], the base maps; missing: the maps restart as after ``reset()``) is required.  ``check`` rejects repeated or out-of-range
+        indices (one synchronisation for a device list); with ``check=False`` the kernel still refuses a record that breaks one of
+        ``set_state``'s rules or names no env: that env is left as it was and ``status()`` shows ST_BAD_STATE.  The generators are not
+        touched; observations are not state: call ``observe`` afterwards."""
+        torch = _torch()
+        specs = self._state_specs()
+        if not isinstance(states, dict):
+            raise ValueError("set_states: expected a dict of tensors")
+        for f in states:
+            if f not in specs:
+                raise ValueError(f"set_states: unknown field {f!r}")
+        for f in _abi.STATE_FIELDS[:-2]:
+            if states.get(f) is None:
+                raise ValueError(f"set_states: {f} is required")
+        given = {f: t for f, t in states.items() if t is not None}
+        if not self.cfg.log_metrics and ("metrics" in given or "visitation" in given):
+            raise ValueError("set_states: the envs keep no counters or visitation maps (log_metrics=False)")
+        first = given["step_count"]
+        n = int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() == 1 else -1
+        if n < 0:
+            raise ValueError("set_states: step_count must be an int32 tensor of shape [n]")
+        if n > self.n_envs:
+            raise ValueError(f"set_states: {n} records for {self.n_envs} envs")
+        arrs = self._state_arrays(given, n, "set_states")
+        ix, m = (None, n) if idx is None else self._index_list(idx, "set_states", check)
+        if m != n:
+            raise ValueError(f"set_states: {n} records but {m} indices")
+        if check and ix is not None and torch.unique(ix).numel() != n:
+            raise ValueError("set_states: repeated indices")
+        if n:
+            self._call("ctf_import_states", C.byref(arrs), _abi.ptr(ix), n, self._stream())
+
     # -- host views ---------------------------------------------------------------------------
     def get_state(self, env_index):
         v = _abi.CtfStateView()
