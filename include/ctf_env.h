@@ -203,7 +203,9 @@ int ctf_step(ctf_env* env, const int8_t* actions_dev, float* rewards_f32_dev, do
 /* standardise_state(i, reverse_grid) + get_env_metadata(i) for every agent of every env
  * (gridworld_ctf.py:975-1009, :1027-1069).
  *   obs_dev      uint8 [E][N][C][G][G] or NULL
- *   meta_dev     IEEE binary16 bits [E][N][M], M = 2N+6, or NULL
+ *   meta_dev     IEEE binary16 bits [E][N][M], M = 2N+6, or NULL.  Must be 8-byte aligned (the rows leave as 8-byte stores; an env's
+ *                N * M * 2 bytes are a multiple of 8): ctf_observe, ctf_observe_codes and ctf_step_observe refuse any other
+ *                pointer with CTF_E_INVALID before anything is launched
  *   reverse_mask bit i = reverse_grid for agent i; CTF_REVERSE_DEFAULT = (team(i) == 1), the value
  *                every caller in the reference passes (ppo.py:69,87; utils.py:535)
  * One launch: k_observe_tiles (one wave per 8 KiB of the flat buffer) when an env's block is a multiple of 16 bytes and at

@@ -335,8 +335,15 @@ static RenderArgs render_args(const ctf_env* h, uint8_t* obs, uint16_t* meta, ui
     return RenderArgs{obs, meta, resolve_reverse(h, reverse_mask), h->sync, h->spin_ticks};
 }
 
+// the metadata rows leave as 8-byte stores (obs_build_env): a caller's meta_dev is refused unless it is 8-byte aligned
+static int meta_arg(const uint16_t* meta, const char* what) {
+    if ((uintptr_t)meta % 8) return fail(CTF_E_INVALID, "%s: meta_dev must be 8-byte aligned", what);
+    return CTF_OK;
+}
+
 extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t reverse_mask, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
+    if (int rc = meta_arg(meta, "ctf_observe")) return rc;
     if (!obs && !meta) return CTF_OK;
     DeviceScope guard(h->device);
     h->d.obs_store_nt = store_hint(h);
@@ -356,6 +363,7 @@ extern "C" int32_t ctf_observe_stores_hinted(const ctf_env* h, const uint8_t* ob
 
 extern "C" int ctf_observe_codes(ctf_env* h, uint8_t* codes, uint16_t* meta, uint16_t* selfcells, uint32_t reverse_mask, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
+    if (int rc = meta_arg(meta, "ctf_observe_codes")) return rc;
     if (!codes && !meta && !selfcells) return CTF_OK;
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_observe_codes(h->d, h->p, codes, meta, selfcells, resolve_reverse(h, reverse_mask), h->n_cus, (hipStream_t)stream));
@@ -365,6 +373,7 @@ extern "C" int ctf_observe_codes(ctf_env* h, uint8_t* codes, uint16_t* meta, uin
 extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, double* rw64, uint8_t* done, uint8_t* obs,
                                 uint16_t* meta, uint32_t reverse_mask, uint32_t flags, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
+    if (int rc = meta_arg(meta, "ctf_step_observe")) return rc;  // before the step: a refused call changes nothing
     DeviceScope guard(h->device);
     // (The ring regeneration rides at the tail of the step launch.  Running it as a launch of its own on a second stream, beside
     // the render, was built and measured in round 3: the render lost more than the step kernel gained — 189-191 M against 198 M
