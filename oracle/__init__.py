@@ -106,6 +106,11 @@ class OracleEnv:
         lib().octf_get_rng_counters(self._h, _ptr(a))
         return int(a[0]), int(a[1])
 
+    def set_rng_counters(self, py_n, np_n):
+        """counter mode: the way back — both tapes continue at these words (after ``seed``, which names the tapes)"""
+        a = np.array([int(py_n), int(np_n)], np.uint64)
+        lib().octf_set_rng_counters(self._h, _ptr(a))
+
     def reset(self):
         lib().octf_reset(self._h)
 

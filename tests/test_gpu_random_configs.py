@@ -38,8 +38,8 @@ def random_scenario(rng, g, n):
 CASES = [(4, 2, 37), (5, 4, 65), (7, 6, 33), (9, 8, 130), (16, 10, 20), (17, 12, 9), (23, 14, 5), (32, 16, 6), (32, 2, 3), (8, 16, 64)]
 
 
-@pytest.mark.parametrize("g,n,n_envs", CASES)
-def test_random_config_matches_oracle(g, n, n_envs):
+def config_kwargs(g, n):
+    """the env kwargs of the case (g, n, ...) of CASES"""
     rng = np.random.default_rng(1000 * g + n)
     scen = random_scenario(rng, g, n)
     kw = dict(
@@ -52,6 +52,12 @@ def test_random_config_matches_oracle(g, n, n_envs):
     )
     if n == 2:  # get_env_metadata indexes agent_hp by TYPE id (gridworld_ctf.py:1041): types must be < N
         kw["AGENT_CONFIG"] = {0: {"team": 0, "type": 1}, 1: {"team": 1, "type": 0}}
+    return kw
+
+
+@pytest.mark.parametrize("g,n,n_envs", CASES)
+def test_random_config_matches_oracle(g, n, n_envs):
+    kw = config_kwargs(g, n)
     log_metrics = bool(g % 2)
     cfg, _ = cfgmod.build_config(kw, log_metrics=log_metrics)
     seeds = np.arange(n_envs, dtype=np.uint64) * 31 + 7
