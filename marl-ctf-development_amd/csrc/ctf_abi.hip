@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "ctf_harvest.h"
 #include "ctf_launch.h"
 #include "ctf_snapshot.h"
+#include "ctf_state_view.h"
 #include "ctf_states.h"
 #include "ctf_visitation.h"
 
@@ -405,47 +407,6 @@ extern "C" int ctf_action_mask(const ctf_env* h, uint8_t* mask_host) {
     return CTF_OK;
 }
 
-// rec / grid / metrics bytes of one env -> the scalar part of its host view
-static void decode_record(const DevCfg& d, const uint8_t* grid, const uint8_t* rec, const int32_t* metrics, ctf_state_view* out, int32_t misc[4]) {
-    memset(out, 0, sizeof(*out));
-    memcpy(out->grid, grid, (size_t)d.GG);
-    for (int i = 0; i < d.N; i++) {
-        memcpy(&out->hp[i], rec + 8 * i, 8);
-        out->pos[i][0] = (int8_t)rec[d.off_pos + 2 * i];
-        out->pos[i][1] = (int8_t)rec[d.off_pos + 2 * i + 1];
-        out->has_flag[i] = rec[d.off_flag + i];
-        out->perm[i] = rec[d.off_perm + i];
-        int16_t inv;
-        memcpy(&inv, rec + d.off_inv + 2 * i, 2);
-        out->inventory[i] = inv;
-    }
-    memcpy(misc, rec + d.off_misc, 16);
-    out->step_count = misc[0];
-    out->team_captures[0] = misc[1];
-    out->team_captures[1] = misc[2];
-    out->done = (misc[3] & CTF_F_DONE) ? 1 : 0;
-    if (metrics)
-        for (int k = 0; k < CTF_N_METRICS; k++)
-            for (int i = 0; i < d.N; i++) out->metrics[k][i] = metrics[(size_t)k * d.N + i];
-}
-
-// visitation maps = base maps (or zeros + 1 at the start cells while nothing has been folded) + the `count` log entries
-// of steps (folded, step_count] (entries[r][i] = agent i's cell after step folded + 1 + r); u8 wrap as in the reference
-static void decode_visitation(const DevCfg& d, const int32_t misc[4], std::vector<uint32_t>& v, const uint16_t* entries, int count,
-                              ctf_state_view* out) {
-    if (misc[3] & CTF_F_BASE_ZERO) {
-        std::fill(v.begin(), v.end(), 0u);
-        for (int i = 0; i < d.N; i++) v[(size_t)i * d.GS + d.start_pos[i][0] * d.G + d.start_pos[i][1]] = 1;  // reset(): :473
-    }
-    for (int r = 0; r < count; r++)
-        for (int i = 0; i < d.N; i++) {
-            const uint16_t cell = entries[(size_t)r * d.N + i];
-            if (cell < (uint16_t)d.GG) v[(size_t)i * d.GS + cell]++;
-        }
-    for (int i = 0; i < d.N; i++)
-        for (int k = 0; k < d.GG; k++) out->visitation[i][k] = (uint8_t)(v[(size_t)i * d.GS + k] & 0xFFu);
-}
-
 extern "C" int ctf_get_state(ctf_env* h, int32_t e, ctf_state_view* out) {
     if (!h || !out) return fail(CTF_E_INVALID, "null argument");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
@@ -456,30 +417,23 @@ extern "C" int ctf_get_state(ctf_env* h, int32_t e, ctf_state_view* out) {
     HIP_TRY(hipMemcpy(grid.data(), h->p.grid + (size_t)e * d.GS, (size_t)d.GS, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rec.data(), h->p.rec + (size_t)e * d.RS, (size_t)d.RS, hipMemcpyDeviceToHost));
     std::vector<int32_t> m((size_t)CTF_N_METRICS * d.N);
-    if (d.log_metrics)
-        HIP_TRY(hipMemcpy(m.data(), h->p.metrics + (size_t)e * CTF_N_METRICS * d.N, m.size() * 4, hipMemcpyDeviceToHost));
+    if (d.log_metrics) HIP_TRY(hipMemcpy(m.data(), h->p.metrics + (size_t)e * CTF_N_METRICS * d.N, m.size() * 4, hipMemcpyDeviceToHost));
     int32_t misc[4];
-    decode_record(d, grid.data(), rec.data(), d.log_metrics ? m.data() : nullptr, out, misc);
+    sv_from_env(state_shape(d), rec.data(), grid.data(), d.log_metrics ? m.data() : nullptr, out, misc);
     if (d.log_metrics) {
         std::vector<uint32_t> v((size_t)d.N * d.GS, 0);
         if (!(misc[3] & CTF_F_BASE_ZERO))
             HIP_TRY(hipMemcpy(v.data(), h->p.vis + (size_t)e * d.N * d.GS, v.size() * 4, hipMemcpyDeviceToHost));
-        const int folded = misc[3] >> CTF_F_FOLDED_SHIFT;
-        const int count = misc[0] - folded;  // <= CTF_VIS_LOG - 1 entries, slots (folded+1 .. step) mod 512
-        std::vector<uint16_t> entries((size_t)(count > 0 ? count : 0) * d.N);
-        if (count > 0) {
-            const size_t pitch = (size_t)d.n_envs * d.N * 2, width = (size_t)d.N * 2;
-            int done_rows = 0;
-            while (done_rows < count) {  // at most two runs: the ring may wrap
-                const int slot = (folded + 1 + done_rows) & (CTF_VIS_LOG - 1);
-                const int rows = (count - done_rows) < (CTF_VIS_LOG - slot) ? (count - done_rows) : (CTF_VIS_LOG - slot);
-                HIP_TRY(hipMemcpy2D(entries.data() + (size_t)done_rows * d.N, width,
-                                    h->p.vislog + ((size_t)slot * d.n_envs + e) * d.N, pitch, width, (size_t)rows,
-                                    hipMemcpyDeviceToHost));
-                done_rows += rows;
-            }
+        // the env's whole log, so that the ONE walk (sv_visitation) indexes it by slot as it does ctf_host_step's; only the window's slots are filled, and read
+        std::unique_ptr<uint16_t[]> ring(new uint16_t[(size_t)CTF_VIS_LOG * d.N]);
+        const size_t pitch = (size_t)d.n_envs * d.N * 2, width = (size_t)d.N * 2;
+        for (int r = 0, rows, count = sv_log_count(misc); r < count; r += rows) {  // at most two runs: the ring may wrap
+            const int slot = sv_log_slot(misc, r);
+            rows = std::min(count - r, CTF_VIS_LOG - slot);
+            HIP_TRY(hipMemcpy2D(ring.get() + (size_t)slot * d.N, width, h->p.vislog + ((size_t)slot * d.n_envs + e) * d.N, pitch, width,
+                                (size_t)rows, hipMemcpyDeviceToHost));
         }
-        decode_visitation(d, misc, v, entries.data(), count > 0 ? count : 0, out);
+        sv_visitation(state_shape(d), d.start_pos, misc, v.data(), ring.get(), (size_t)d.N, out);
     }
     return CTF_OK;
 }
@@ -508,7 +462,7 @@ __global__ void __launch_bounds__(256) k_host_pack(DevCfg d, DevPtrs p, uint8_t*
         uint32_t* m = (uint32_t*)(io + L.metrics);
         for (int k = t; k < CTF_N_METRICS * d.N; k += 256) m[k] = (uint32_t)p.metrics[k];
         uint32_t* v = (uint32_t*)(io + L.vis);
-        for (int k = t; k < d.N * d.GS; k += 256) v[k] = p.vis[k];
+        for (int k = t; k < d.N * d.GS; k += 256) v[k] = p.vis[k];  // ALL N * GS words, in every call: ctf_host_step counts in them in place
         uint32_t* lg = (uint32_t*)(io + L.vislog);
         const uint32_t* src = (const uint32_t*)p.vislog;  // n_envs == 1: the ring [512][N] u16 is contiguous, N even or odd: 512 * N * 2 bytes
         for (int k = t; k < CTF_VIS_LOG * d.N / 2; k += 256) lg[k] = src[k];
@@ -579,20 +533,23 @@ extern "C" int ctf_host_step(ctf_env* h, const int8_t* actions, const uint32_t* 
     int32_t misc[4];
     ctf_state_view local;
     ctf_state_view* out = view ? view : &local;
-    decode_record(d, hh + L.grid, hh + L.rec, d.log_metrics ? (const int32_t*)(hh + L.metrics) : nullptr, out, misc);
+    sv_from_env(state_shape(d), hh + L.rec, hh + L.grid, d.log_metrics ? (const int32_t*)(hh + L.metrics) : nullptr, out, misc);
     if (done) *done = out->done;
-    if (view && d.log_metrics) {
-        std::vector<uint32_t> v((size_t)d.N * d.GS);
-        memcpy(v.data(), hh + L.vis, v.size() * 4);
-        const int folded = misc[3] >> CTF_F_FOLDED_SHIFT;
-        const int count = misc[0] - folded;
-        std::vector<uint16_t> entries((size_t)(count > 0 ? count : 0) * d.N);
-        const uint16_t* ring = (const uint16_t*)(hh + L.vislog);
-        for (int r = 0; r < count; r++)
-            memcpy(entries.data() + (size_t)r * d.N, ring + (size_t)((folded + 1 + r) & (CTF_VIS_LOG - 1)) * d.N, (size_t)d.N * 2);
-        decode_visitation(d, misc, v, entries.data(), count > 0 ? count : 0, out);
+    if (view && d.log_metrics) {  // (the block's base maps become the counts in place: k_host_pack writes them afresh in every call)
+        sv_visitation(state_shape(d), d.start_pos, misc, (uint32_t*)(hh + L.vis), (const uint16_t*)(hh + L.vislog), (size_t)d.N, out);
     }
     return CTF_OK;
+}
+
+// the text of a view's refusal: the first value, in the view's order, that breaks one of ctf_states.h's rules
+static int refused_view(const DevCfg& d, const ctf_state_view* in) {
+    for (int i = 0; i < d.N; i++) {
+        if (!st_ok_coord(in->pos[i][0], d.G) || !st_ok_coord(in->pos[i][1], d.G)) return fail(CTF_E_INVALID, "pos[%d] outside the grid", i);
+        if (!st_ok_perm(in->perm[i], d.N)) return fail(CTF_E_INVALID, "perm[%d]", i);
+        if (!st_ok_inventory(in->inventory[i])) return fail(CTF_E_INVALID, "inventory[%d]", i);
+    }
+    for (int k = 0; k < d.GG; k++) if (!st_ok_tile(in->grid[k])) return fail(CTF_E_INVALID, "grid[%d]", k);
+    return st_ok_step(in->step_count) ? fail(CTF_E_INVALID, "invalid view") : fail(CTF_E_INVALID, "step_count %d", in->step_count);
 }
 
 extern "C" int ctf_set_state(ctf_env* h, int32_t e, const ctf_state_view* in) {
@@ -600,41 +557,16 @@ extern "C" int ctf_set_state(ctf_env* h, int32_t e, const ctf_state_view* in) {
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
     DeviceScope guard(h->device);
     const DevCfg& d = h->d;
-    for (int i = 0; i < d.N; i++) {
-        if (in->pos[i][0] < 0 || in->pos[i][0] >= d.G || in->pos[i][1] < 0 || in->pos[i][1] >= d.G)
-            return fail(CTF_E_INVALID, "pos[%d] outside the grid", i);
-        if (in->perm[i] >= d.N) return fail(CTF_E_INVALID, "perm[%d]", i);
-        if (in->inventory[i] < 0 || in->inventory[i] > 1000) return fail(CTF_E_INVALID, "inventory[%d]", i);
-    }
-    for (int k = 0; k < d.GG; k++)
-        if (in->grid[k] > 13) return fail(CTF_E_INVALID, "grid[%d]", k);
-    if (in->step_count < 0 || in->step_count >= (1 << 28)) return fail(CTF_E_INVALID, "step_count %d", in->step_count);
+    std::vector<uint8_t> rec((size_t)d.RS), grid((size_t)d.GS);
+    std::vector<int32_t> m(d.log_metrics ? (size_t)CTF_N_METRICS * d.N : 0);
+    std::vector<uint32_t> v(d.log_metrics ? (size_t)d.N * d.GS : 0);
+    if (!sv_to_env(state_shape(d), in, rec.data(), grid.data(), d.log_metrics ? m.data() : nullptr, d.log_metrics ? v.data() : nullptr))
+        return refused_view(d, in);
     HIP_TRY(hipDeviceSynchronize());
-    std::vector<uint8_t> rec((size_t)d.RS, 0), grid((size_t)d.GS, 0);
-    memcpy(grid.data(), in->grid, (size_t)d.GG);
-    for (int i = 0; i < d.N; i++) {
-        memcpy(rec.data() + 8 * i, &in->hp[i], 8);
-        rec[d.off_pos + 2 * i] = (uint8_t)in->pos[i][0];
-        rec[d.off_pos + 2 * i + 1] = (uint8_t)in->pos[i][1];
-        rec[d.off_flag + i] = in->has_flag[i];
-        rec[d.off_perm + i] = in->perm[i];
-        const int16_t inv = (int16_t)in->inventory[i];
-        memcpy(rec.data() + d.off_inv + 2 * i, &inv, 2);
-    }
-    // the given visitation maps become the base maps; the log is empty (folded up to step_count)
-    const int32_t misc[4] = {in->step_count, in->team_captures[0], in->team_captures[1],
-                             (in->done ? CTF_F_DONE : 0) | (d.log_metrics ? 0 : CTF_F_BASE_ZERO) | (in->step_count << CTF_F_FOLDED_SHIFT)};
-    memcpy(rec.data() + d.off_misc, misc, 16);
     HIP_TRY(hipMemcpy(h->p.grid + (size_t)e * d.GS, grid.data(), (size_t)d.GS, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->p.rec + (size_t)e * d.RS, rec.data(), (size_t)d.RS, hipMemcpyHostToDevice));
     if (d.log_metrics) {
-        std::vector<int32_t> m((size_t)CTF_N_METRICS * d.N);
-        for (int k = 0; k < CTF_N_METRICS; k++)
-            for (int i = 0; i < d.N; i++) m[(size_t)k * d.N + i] = in->metrics[k][i];
         HIP_TRY(hipMemcpy(h->p.metrics + (size_t)e * CTF_N_METRICS * d.N, m.data(), m.size() * 4, hipMemcpyHostToDevice));
-        std::vector<uint32_t> v((size_t)d.N * d.GS, 0);
-        for (int i = 0; i < d.N; i++)
-            for (int k = 0; k < d.GG; k++) v[(size_t)i * d.GS + k] = in->visitation[i][k];
         HIP_TRY(hipMemcpy(h->p.vis + (size_t)e * d.N * d.GS, v.data(), v.size() * 4, hipMemcpyHostToDevice));
     }
     return CTF_OK;

@@ -9,9 +9,9 @@
 // the two directions and the two widths cannot disagree.  Work items are taken t, t + nt, t + 2 nt, ...: consecutive lanes of a
 // record's group touch consecutive words of a row.
 //
-// EXPORT shows what ctf_get_state's decode_record shows: the record's fields as they lie (hp is eight bytes, copied), inventory
-// widened from i16, step / captures = misc[0..2], done = misc[3] & CTF_F_DONE.
-// IMPORT writes what ctf_set_state writes, byte for byte: the record with its unused bytes zero, the grid with GG..GS zero, the
+// EXPORT shows what ctf_get_state shows (it runs these functions on one record, ctf_state_view.h): the record's fields as they lie (hp
+// is eight bytes, copied), inventory widened from i16, step / captures = misc[0..2], done = misc[3] & CTF_F_DONE.
+// IMPORT writes what ctf_set_state writes (likewise), byte for byte: the record with its unused bytes zero, the grid with GG..GS zero, the
 // counters (zeros when none are given), and either the given u8 maps widened into the u32 base maps (pad cells zero) or
 // CTF_F_BASE_ZERO; misc[3] = done | base-zero | step_count << CTF_F_FOLDED_SHIFT: the visitation log is empty.
 // All offsets into caller arrays and env state are size_t.
@@ -116,22 +116,29 @@ CTF_HD void states_unpack(const StateShape& S, const uint8_t* rec, const uint8_t
 // ---- import: row -> device form -----------------------------------------------------------------------------------------------------
 CTF_HD const uint8_t* st_row(const StateShape& S, const StateArrays& in, int f, size_t k) { return in.arr[f] + k * (size_t)st_row_bytes(S, f); }
 
-// ctf_set_state's checks on row k (the items t, t + nt, ... of them): true = nothing wrong among these items
+// what a record may hold, one predicate per rule: states_check applies them to a row, ctf_set_state names the first value that breaks one
+CTF_HD bool st_ok_coord(const int8_t& v, const int32_t& G) { return v >= 0 && v < G; }  // a row or column inside the grid (by reference: k_import_states keeps its code)
+CTF_HD bool st_ok_perm(int v, int N) { return v < N; }                     // an entry of the shuffled agent order
+CTF_HD bool st_ok_inventory(int32_t v) { return v >= 0 && v <= 1000; }     // (the record keeps it as i16)
+CTF_HD bool st_ok_tile(int v) { return v <= 13; }                          // a grid code
+CTF_HD bool st_ok_step(int32_t v) { return v >= 0 && v < (1 << 28); }      // (misc[3] keeps step_count << CTF_F_FOLDED_SHIFT)
+
+// the rules on row k (the items t, t + nt, ... of them): true = nothing wrong among these items
 CTF_HD bool states_check(const StateShape& S, const StateArrays& in, size_t k, int t, int nt) {
     bool ok = true;
     const int8_t* pos = (const int8_t*)st_row(S, in, ST_POS, k);
-    for (int j = t; j < 2 * S.N; j += nt) ok = ok && pos[j] >= 0 && pos[j] < S.G;
+    for (int j = t; j < 2 * S.N; j += nt) ok = ok && st_ok_coord(pos[j], S.G);
     const uint8_t* perm = st_row(S, in, ST_PERM, k);
     const uint8_t* inv = st_row(S, in, ST_INV, k);
     for (int i = t; i < S.N; i += nt) {
         const int32_t v = (int32_t)st_load_u32(inv + 4 * i);
-        ok = ok && perm[i] < S.N && v >= 0 && v <= 1000;
+        ok = ok && st_ok_perm(perm[i], S.N) && st_ok_inventory(v);
     }
     const uint8_t* grid = st_row(S, in, ST_GRID, k);
-    for (int c = t; c < S.GG; c += nt) ok = ok && grid[c] <= 13;
+    for (int c = t; c < S.GG; c += nt) ok = ok && st_ok_tile(grid[c]);
     if (t == 0) {
         const int32_t step = (int32_t)st_load_u32(st_row(S, in, ST_STEP, k));
-        ok = ok && step >= 0 && step < (1 << 28);
+        ok = ok && st_ok_step(step);
     }
     return ok;
 }

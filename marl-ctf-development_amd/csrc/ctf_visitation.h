@@ -1,7 +1,7 @@
 // ctf_visitation.h — what the visitation harvest and export (ctf_harvest_visitation / ctf_export_visitation, ctf_visitation.hip)
 // need of a handle, and the definition of the result.  Shared by the host code (ctf_abi.hip) and the kernels.
 //
-// THE MAP OF ONE ENV is what the host decode (decode_visitation, ctf_abi.hip) computes before its final `& 0xFF`.  For agent i:
+// THE MAP OF ONE ENV is what the host decode (sv_visitation, ctf_state_view.h) computes before its final `& 0xFF`.  For agent i:
 //   base   CTF_F_BASE_ZERO set in the env's misc flags: zeros, plus 1 at start_pos[i];  otherwise vis[e][i][:] (u32)
 //   log    + 1 at cell vislog[s & 511][e][i] for every step s in (folded, env_step_count], folded = misc[3] >> CTF_F_FOLDED_SHIFT
 //          (at most 511 entries: k_step folds its own log before a slot is reused)

@@ -493,6 +493,59 @@ def test_refusals():
         v.close()
 
 
+def test_set_state_names_the_broken_rule_and_writes_nothing():
+    """The per-env call's own refusals: one value broken per rule in a view that ``get_state`` gave; the message names the rule and
+    the index, no env's bytes change, and the values on the legal side of every bound go in and come back."""
+    E, K = 4, 2
+    vec, _ = _make(E, Case("fuzz_06").kwargs)  # 7 x 7, two agents
+    n, g = vec.N_AGENTS, vec.GRID_SIZE
+    assert (n, g) == (2, 7)
+    _run(vec, _acts(vec), 0, 5, auto_reset=False)
+    before = vec.save_states().clone()
+
+    def broken(change):
+        view = vec.get_state(K)
+        change(view)
+        return view
+
+    def put(member, where, value):
+        def change(view):
+            target = getattr(view, member)
+            for w in where[:-1]:
+                target = target[w]
+            target[where[-1]] = value
+        return change
+
+    rules = [(put("pos", (1, 0), g), "pos[1] outside the grid"), (put("perm", (0,), n), "perm[0]"), (put("inventory", (1,), 1001), "inventory[1]"),
+             (put("inventory", (1,), -1), "inventory[1]"), (put("grid", (3,), 14), "grid[3]"),
+             (lambda v: setattr(v, "step_count", -1), "step_count -1"), (lambda v: setattr(v, "step_count", 1 << 28), f"step_count {1 << 28}")]
+    for change, text in rules:
+        with pytest.raises(abi.CtfLibraryError) as err:
+            vec.set_state(K, broken(change))
+        assert text in str(err.value), (text, str(err.value))
+        assert "(-1)" in str(err.value)  # CTF_E_INVALID
+        assert torch.equal(vec.save_states(), before), text
+    with pytest.raises(abi.CtfLibraryError) as err:
+        vec.set_state(E, vec.get_state(K))
+    assert "(-4)" in str(err.value) and f"env index {E}" in str(err.value)  # CTF_E_RANGE
+    assert torch.equal(vec.save_states(), before) and vec.status() == 0
+
+    # the valid extremes round-trip
+    def extremes(view):
+        view.inventory[0], view.inventory[1], view.step_count, view.done = 0, 1000, (1 << 28) - 1, 7
+    held = view_arrays(vec.get_state(K), n, g)
+    vec.set_state(K, broken(extremes))
+    got = view_arrays(vec.get_state(K), n, g)
+    assert got["inv"].tolist() == [0, 1000] and got["step_count"] == (1 << 28) - 1 and got["done"] == 1
+    for f in ("grid", "pos", "has_flag", "perm", "team_captures", "metrics", "visitation"):
+        assert np.array_equal(got[f], held[f]), f
+    assert np.array_equal(_bits(got["hp"]), _bits(held["hp"]))
+    after = vec.save_states()
+    rest = [e for e in range(E) if e != K]
+    assert torch.equal(after[rest], before[rest]) and not torch.equal(after[K], before[K]) and vec.status() == 0
+    vec.close()
+
+
 # ---- 6. capture ----------------------------------------------------------------------------------------------------------------------
 def test_step_observe_and_export_replayed_from_a_graph():
     E, kw = 70, _arena(GAME_STEPS=50)

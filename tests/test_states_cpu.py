@@ -221,7 +221,8 @@ def test_the_recorder_pads_to_16_makes_one_call_per_frame_and_trims():
 # ---- the conversion both kernels share, under sanitizers -----------------------------------------------------------------------
 def test_the_shared_conversion_under_sanitizers():
     """tests/hostsim/states_main.cpp: a stand-alone program (its own main, the sanitizer runtimes linked in) that runs
-    ctf_states.h's pack / unpack / check over exactly-sized heap buffers."""
+    ctf_states.h's pack / unpack / check, and the per-env view functions of ctf_state_view.h built on them, over exactly-sized heap
+    buffers."""
     cxx = "/opt/rocm/lib/llvm/bin/clang++"
     if not os.path.exists(cxx):
         cxx = "clang++"
