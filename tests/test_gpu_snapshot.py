@@ -417,3 +417,35 @@ def test_full_size_round_trip_both_launch_modes(mode, path, monkeypatch):
     two launches (k_step + the tile render) and one (k_step_observe).  The final records are compared as _same_records says: at
     this size the step kernel's ring regeneration is not deterministic in its timing, only in its results."""
     _roundtrip(65536, mode, True, monkeypatch=monkeypatch, path=path, exact=False)
+
+
+def test_the_reward_constants_are_part_of_the_fingerprint(monkeypatch):
+    """ctf_snapshot.h hashes the six reward constants of the config; the env kwargs cannot vary them, so no other test does.  Two
+    handles that differ in ``reward_tag`` alone (tests/_rule_cases.py edits the config build_config returns) have different
+    fingerprints and each refuses the other's records, env untouched; so does a change of any other of the six."""
+    import _rule_cases as rc
+
+    seeds = np.arange(8, dtype=np.uint64) + 3
+    make = lambda consts: rc.open_vec(monkeypatch, "tag", consts, 8, device=0, py_seeds=seeds, np_seeds=seeds)
+    a, twin, b = make("VIS"), make("VIS"), make(dict(rc.VIS, reward_tag=0.41))
+    assert a.fingerprint == twin.fingerprint and a.fingerprint != b.fingerprint and a.snapshot_bytes == b.snapshot_bytes
+    acts = torch.full((8, a.N_AGENTS), 1, dtype=torch.int8, device=a.device)
+    for vec in (a, b):
+        vec.step(acts)
+    for src, dst in ((a, b), (b, a)):
+        recs, before = src.save_states(), dst.save_states()
+        dst.load_states(recs)
+        assert dst.status() == abi.ST_BAD_SNAPSHOT
+        assert torch.equal(dst.save_states(), before), "a refused record changed an env"
+        assert src.status() == 0
+    twin.load_states(a.save_states())
+    assert twin.status() == 0 and torch.equal(twin.save_states(), a.save_states())
+    fps = {a.fingerprint, b.fingerprint}
+    for field in rc.VIS:
+        if field != "reward_tag":
+            other = make(dict(rc.VIS, **{field: rc.VIS[field] + 0.25}))
+            fps.add(other.fingerprint)
+            other.close()
+    assert len(fps) == 7, "every one of the six constants changes the fingerprint"
+    for vec in (a, twin, b):
+        vec.close()
