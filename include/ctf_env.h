@@ -223,7 +223,13 @@ int ctf_step(ctf_env* env, const int8_t* actions_dev, float* rewards_f32_dev, do
  * observation buffer: knobs placement_tries (default 256 candidates, CTF_PLACEMENT_TRIES), CTF_PLACEMENT_SECONDS (default 3.0: once a
  * buffer of the fast kind is in hand the search for a better one ends after this long; ten seconds while none has turned up) and placement_gib (default 16: the cap
  * on what the search may HOLD — it holds two buffers, the candidate and the best so far; CTF_PLACEMENT_GIB), tune_placement=False
- * to switch it off; VecGridworldCtf.placement reports kind, ratio, candidates tried, bytes held and the time it took. */
+ * to switch it off; VecGridworldCtf.placement reports kind, ratio, candidates tried, bytes held and the time it took.
+ *
+ * INVALIDATION RULE.  ctf_observe and ctf_step_observe write EVERY byte of obs_dev — except into the one buffer the caller has
+ * handed over with ctf_obs_retain (below): there they rewrite only the 128-byte lines whose bytes differ from what this handle
+ * last rendered into it.  Whoever else writes into a retained buffer (a fill, a copy, another handle, another library) must call
+ * ctf_obs_invalidate before the next render; changes of the env STATE (ctf_reset, auto-reset, ctf_set_state, ctf_import_states,
+ * ctf_load_states) and of reverse_mask need no notice. */
 #define CTF_REVERSE_DEFAULT 0xFFFFFFFFu
 int ctf_observe(ctf_env* env, uint8_t* obs_dev, uint16_t* meta_dev, uint32_t reverse_mask, void* stream);
 /* which of the two a ctf_observe into obs_dev launches: 1 = k_observe_tiles, 0 = k_observe (profiling: attributing a measured
@@ -232,6 +238,29 @@ int32_t ctf_observe_kernel(const ctf_env* env, const uint8_t* obs_dev);
 /* 1 when that launch stores the observation with the nontemporal hint (the tile kernel while the live handles' observations on
  * the device exceed 320 MB, or CTF_OBS_NT=1), 0 for plain stores */
 int32_t ctf_observe_stores_hinted(const ctf_env* env, const uint8_t* obs_dev);
+
+/* RETAINED observations: rewrite only what changed.  Per env-step about 15 % of the 128-byte lines of an arena env's block differ
+ * from the step before; a buffer that only this handle writes need not be rewritten whole.
+ * Retention is opted into, never inferred: the address of a buffer proves nothing about its contents (an allocator hands the same
+ * address out again; a caller fills its buffer), so every pointer that has not been retained keeps the meaning above.
+ * ctf_obs_retain: the caller promises that from now on only this handle writes obs_dev, a full [E][N][C][G][G] block.  One retained
+ *   buffer per handle; a second call replaces the first; obs_dev = NULL releases it.  Retaining invalidates: the next render
+ *   into the buffer writes everything.  The first call allocates the handle's SHADOW on the device — per env the grid and the
+ *   position bytes the buffer's block was last rendered from, and one key word that names the reverse mask of that render or
+ *   says "unknown" (about 270 bytes per arena env) — and the call waits for `stream` once (everything after it is capturable;
+ *   on a stream that is being captured the call retains nothing and renders stay full).  Renders into the retained buffer are then k_observe_delta: one wave per env compares the state with the shadow, and
+ *   rewrites the dirty lines (all of them where the key is not the expected one) and the metadata rows.  Validity is device
+ *   state only, so a hipGraph captured before the shadow was ever written replays correctly.  The delta render applies when
+ *   an env's block is a multiple of 16 bytes, at most 261 904 of them (a span of 2 048 lines), and obs_dev is 16-byte aligned; otherwise, and with
+ *   CTF_OBS_RETAIN=0 in the environment (read at the call), ctf_obs_retain is a no-op and renders stay full.
+ *   CTF_STEP_OBSERVE_ONE_LAUNCH=1 wins over retention: that launch renders in full and invalidates.  The delta render's
+ *   stores carry the nontemporal hint by the full render's rule (above); CTF_OBS_DELTA_NT=0 / 1 at the call forces it off / on.
+ * ctf_obs_invalidate: everything about the retained buffer is unknown again.  Stream-ordered, one small launch, capturable.
+ * ctf_observe_retained: 1 if a ctf_observe into obs_dev would take the delta path now, else 0.
+ * A render with obs_dev = NULL (metadata only) or into any other pointer leaves the shadow alone. */
+int ctf_obs_retain(ctf_env* env, uint8_t* obs_dev, void* stream);
+int ctf_obs_invalidate(ctf_env* env, void* stream);
+int32_t ctf_observe_retained(const ctf_env* env, const uint8_t* obs_dev);
 
 /* The same observation in compact form: the tile planes 1..C-1 of standardise_state are one-hot per cell
  * (plane k+1 = (relabelled grid == TILES_USED[k]), gridworld_ctf.py:990-1001) and plane 0 holds the single

@@ -140,6 +140,9 @@ SYMBOLS = {
     "ctf_observe": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "ctf_observe_kernel": (C.c_int32, [_P, _P]),
     "ctf_observe_stores_hinted": (C.c_int32, [_P, _P]),
+    "ctf_obs_retain": (C.c_int, [_P, _P, _P]),
+    "ctf_obs_invalidate": (C.c_int, [_P, _P]),
+    "ctf_observe_retained": (C.c_int32, [_P, _P]),
     "ctf_observe_codes": (C.c_int, [_P, _P, _P, _P, C.c_uint32, _P]),
     "ctf_step_observe": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     "ctf_step_observe_launches": (C.c_int32, [_P, _P]),

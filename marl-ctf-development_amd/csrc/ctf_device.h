@@ -109,6 +109,17 @@ struct DevPtrs {
     uint32_t* status;
 };
 
+// The shadow of a handle's RETAINED observation buffer (ctf_obs_retain): what was last rendered into it — never a record of what
+// a step did.  Allocated at the first ctf_obs_retain.  key[e] == CTF_OBS_KEY(m) says "grid[e] / pos[e] are the state env e's
+// block of the retained buffer was rendered from, under reverse mask m"; anything else (0 after an invalidation) says nothing is
+// known about that block.  Only k_observe_delta reads and writes grid / pos; the key is also cleared by k_obs_key_clear.
+struct ObsShadow {
+    uint8_t* grid;   // u8  [E][GS]
+    uint16_t* pos;   // u16 [E][CTF_MAX_AGENTS]: agent i's (row, col) bytes as the record holds them
+    uint32_t* key;   // u32 [E]
+};
+#define CTF_OBS_KEY(reverse_mask) (0x80000000u | (uint32_t)(reverse_mask))
+
 // rec.misc[3]: bit 0 done, bit 1 base maps are implicitly zero (+1 at the start cells), bits 2.. = last step whose
 // log entry has been folded into the base maps
 #define CTF_F_DONE 1

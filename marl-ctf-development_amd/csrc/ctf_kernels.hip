@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "ctf_launch.h"
+#include "ctf_obs_delta.h"
 // Profiling-only phase trace of the step kernel (tools/trace_step.py): lane 0 of every block stamps the 100 MHz wall clock at
 // fixed points (0 start, 1 staged, 7 hit bits, 5 ring, 6 shuffle 1, 8/9/10 + 3 k act / tagging / metrics of turn k, 32 turns
 // done, 33 shuffle 2, 34 stepped, 2 barrier, 3 written back, 4 end); never defined in the shipped build.
@@ -713,6 +714,161 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
 }
 
 // ------------------------------------------------------------------------------------------------
+// observe into a RETAINED buffer — only the 128-byte lines whose bytes changed since the last render into it
+// ------------------------------------------------------------------------------------------------
+// The caller has promised (ctf_obs_retain) that nobody but this handle writes the buffer, and the handle keeps a shadow of what it
+// last rendered there (ObsShadow, ctf_device.h).  One wave per env, one env per wave:
+//   1. all loads first: the env's record and grid, the shadow's grid and positions, the shadow's key;
+//   2. the env's bitmap and its metadata rows exactly as k_observe makes them (obs_build_env: the rows are written whole);
+//   3. the dirty lines of the env's span (ctf_obs_delta.h has the rule): XOR of the two grids names the changed cells, a moved
+//      viewer its two bytes of plane 0; a key that is not the expected one makes every line dirty — that is the first render,
+//      an invalidation and a change of the reverse mask, with no other code for any of them;
+//   4. the dirty lines' indices compacted into a list (popcount prefix over the mask dwords), then eight lines per store
+//      instruction: lanes 8k .. 8k+7 write the eight 16-byte chunks of the k-th line of the pass from the bitmap; chunks outside
+//      the env's own block belong to the neighbour's wave and are skipped (blocks are whole chunks);
+//   5. the shadow dwords that differ are written back, and the key where it was not the expected one.
+// State that changed behind the render (reset, auto-reset, set_state, import, restore) needs no notice: the shadow is compared
+// with the state itself.  Envs go to XCDs in contiguous eighths as in k_observe.
+// Per-wave LDS: [rec RS][mvals 96][meta staging][bitmap][line mask][line list u16].
+__host__ __device__ inline int delta_mask_bytes(int obs_bytes) { return ((obsd_lines(obs_bytes, CTF_OBS_LINE - 16) + 31) / 32 * 4 + 15) & ~15; }
+__host__ __device__ inline int delta_list_bytes(int obs_bytes) { return (obsd_lines(obs_bytes, CTF_OBS_LINE - 16) * 2 + 15) & ~15; }
+__host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int obs_bytes) {
+    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_bitmap_bytes(obs_bytes) + delta_mask_bytes(obs_bytes) + delta_list_bytes(obs_bytes);
+}
+#define OBS_DELTA_UNROLL 4  // store instructions (of eight lines each) per pass, their bitmap halfwords read first
+
+template <int STORE_NT>
+__global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
+                                                                     uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map) {
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4;
+    const uint32_t b = blockIdx.x;
+    const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
+    const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
+    if (e >= cfg.n_envs) return;  // (the whole wave: nothing below synchronises across waves)
+    uint8_t* wl = (uint8_t*)lds + wave * delta_wave_bytes(cfg.RS, N, M, OB);
+    uint8_t* srec = wl;
+    uint16_t* mv = (uint16_t*)(wl + cfg.RS);
+    uint16_t* mstage = (uint16_t*)(wl + cfg.RS + OBS_MV_BYTES);
+    uint32_t* bits = (uint32_t*)(wl + cfg.RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M));
+    uint32_t* lmask = (uint32_t*)((uint8_t*)bits + obs_bitmap_bytes(OB));
+    uint16_t* llist = (uint16_t*)((uint8_t*)lmask + delta_mask_bytes(OB));
+
+    // ---- 1. loads, all issued before anything waits, on clamped indices
+    const uint32_t* gcur = (const uint32_t*)(p.grid + (size_t)e * cfg.GS);
+    uint32_t* gsh = (uint32_t*)(sh.grid + (size_t)e * cfg.GS);
+    const uint32_t recw = ((const uint32_t*)(p.rec + (size_t)e * cfg.RS))[min(lane, cfg.RS / 4 - 1)];
+    uint32_t cur[4], old[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {  // G <= 32: at most 256 grid dwords (uniform conditions)
+        cur[j] = (GW > WAVE * j) ? gcur[min(lane + WAVE * j, GW - 1)] : 0u;
+        old[j] = (GW > WAVE * j) ? gsh[min(lane + WAVE * j, GW - 1)] : 0u;
+    }
+    uint16_t* psh = sh.pos + (size_t)e * CTF_MAX_AGENTS;
+    const uint32_t old_pos = psh[min(lane, N - 1)];
+    const uint32_t key = CTF_OBS_KEY(reverse_mask);
+    const bool known = sh.key[e] == key;  // uniform
+
+    // ---- 2. bitmap + metadata rows
+    if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
+    const ObsSlots slots = obs_slots(cfg, reverse_mask);
+    obs_build_env(cfg, p, e, recw, cur[0], srec, mv, mstage, p.meta_lut, bits, slots, reverse_mask, lane, true, meta);
+
+    // ---- 3. the dirty lines of the env's span
+    const size_t base = (size_t)e * (size_t)OB;
+    const int lead = (int)(((uintptr_t)obs + base) & (uintptr_t)(CTF_OBS_LINE - 1));  // a multiple of 16
+    const int nl = obsd_lines(OB, lead), ndw = (nl + 31) >> 5;                       // ndw <= 64 (obsd_applies)
+    if (lane < ndw) {
+        const int left = nl - 32 * lane;
+        lmask[lane] = known ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
+    }
+    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t cur_pos = *(const uint16_t*)(srec + cfg.off_pos + 2 * min(lane, N - 1));
+    if (known) {
+        ObsDeltaShape s;
+        s.N = N; s.G = cfg.G; s.GG = cfg.GG; s.CGG = cfg.CGG; s.obs_bytes = OB; s.flip_axis = cfg.flip_axis;
+        s.team_mask = cfg.team_mask; s.chan_lut[0] = cfg.chan_lut[0]; s.chan_lut[1] = cfg.chan_lut[1];
+        auto mark = [&](int line) {
+            if ((uint32_t)line < (uint32_t)nl) atomicOr(lmask + (line >> 5), 1u << (line & 31));
+        };
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int w = lane + WAVE * j;
+            const uint32_t x = cur[j] ^ old[j];
+            if (GW > WAVE * j && w < GW && x) {
+                for (int q = 0; q < 4; q++) {
+                    const int cell = 4 * w + q;
+                    if (((x >> (8 * q)) & 0xFFu) && cell < cfg.GG)
+                        obsd_cell_changed(s, reverse_mask, lead, cell, (old[j] >> (8 * q)) & 0xFFu, (cur[j] >> (8 * q)) & 0xFFu, mark);
+                }
+            }
+        }
+        if (lane < N && cur_pos != old_pos) {
+            const int oc = (int)(int8_t)(old_pos & 0xFFu) * cfg.G + (int)(int8_t)(old_pos >> 8);
+            const int nc = (int)(int8_t)(cur_pos & 0xFFu) * cfg.G + (int)(int8_t)(cur_pos >> 8);
+            obsd_viewer_moved(s, reverse_mask, lead, lane, oc, nc, mark);
+        }
+        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    // ---- 4. compact: lane q lists the set bits of mask dword q behind those of the dwords before it
+    uint32_t m = lane < ndw ? lmask[lane] : 0u;
+    int incl = __popc(m);
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int up = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += up;
+    }
+    const int total = __shfl(incl, WAVE - 1, WAVE);
+    for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
+    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+    __builtin_amdgcn_wave_barrier();
+    // ... and emit: lanes 8k .. 8k+7 hold the eight chunks of one line
+    {
+        uint8_t* out = obs + base;
+        const uint16_t* hb = (const uint16_t*)bits;
+        const int sub = lane >> 3, off_in_line = (lane & 7) * 16 - lead;
+        for (int l0 = 0; l0 < total; l0 += 8 * OBS_DELTA_UNROLL) {
+            uint32_t h[OBS_DELTA_UNROLL];
+            int k[OBS_DELTA_UNROLL];
+#pragma unroll
+            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
+                const int idx = l0 + 8 * u + sub;
+                const int o = idx < total ? (int)llist[idx] * CTF_OBS_LINE + off_in_line : -1;  // byte of the env's block
+                k[u] = (o >= 0 && o < OB) ? o >> 4 : -1;
+                h[u] = k[u] >= 0 ? hb[k[u]] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
+                if (k[u] >= 0) {
+                    const u32x4_t v = {expand4(h[u], 0), expand4(h[u], 1), expand4(h[u], 2), expand4(h[u], 3)};
+                    if (STORE_NT) __builtin_nontemporal_store(v, (u32x4_t*)(out + ((size_t)k[u] << 4)));
+                    else *(u32x4_t*)(out + ((size_t)k[u] << 4)) = v;
+                }
+            }
+        }
+    }
+
+    // ---- 5. the shadow follows what the buffer now holds
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int w = lane + WAVE * j;
+        if (GW > WAVE * j && w < GW && (!known || cur[j] != old[j])) gsh[w] = cur[j];
+    }
+    if (lane < N && (!known || cur_pos != old_pos)) psh[lane] = (uint16_t)cur_pos;
+    if (!known && lane == 0) sh.key[e] = key;
+}
+// Everything about the retained buffer is unknown again (ctf_obs_invalidate; behind every other launch that writes the buffer)
+extern "C" __global__ void k_obs_key_clear(uint32_t* key, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) key[i] = 0u;
+}
+
+// ------------------------------------------------------------------------------------------------
 // observe as one-shot TILES — the same bitmap idea, organised by output address instead of by env
 // ------------------------------------------------------------------------------------------------
 // Wave t of the grid renders CTF_OBS_TILE (8 192) consecutive bytes of the FLAT observation buffer and exits: it loads the
@@ -1302,6 +1458,29 @@ extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, co
     if (align == 16) hipLaunchKernelGGL(k_observe<16>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
     else if (align == 4) hipLaunchKernelGGL(k_observe<4>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
     else hipLaunchKernelGGL(k_observe<1>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
+    return hipGetLastError();
+}
+// the one rule by which a render into a retained `obs` can be the delta render: whole 16-byte chunks at 16-byte aligned addresses
+// and a span of lines the kernel's mask holds (ctf_obs_delta.h)
+extern "C" int ctf_observe_delta_applies(const DevCfg& cfg, const uint8_t* obs) {
+    return obs && ((uintptr_t)obs % 16) == 0 && obsd_applies(cfg.obs_bytes);
+}
+// k_observe_delta: one wave per env, up to 4 independent waves per block, a multiple of 8 blocks (XCD-contiguous envs)
+extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs& p, const ObsShadow& shadow, const RenderArgs& r, int store_nt,
+                                               hipStream_t st) {
+    const int per_wave = delta_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes);
+    const int wpb = obs_waves_per_block(per_wave);
+    const size_t sh = (size_t)wpb * per_wave;
+    const unsigned blocks = (unsigned)(((cfg.n_envs + wpb - 1) / wpb + 7) / 8 * 8);
+    const uint32_t xcd_map = obs_xcd_knob();
+    with_bool(store_nt != 0, [&](auto NT) {
+        hipLaunchKernelGGL(k_observe_delta<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta, r.reverse_mask,
+                           xcd_map);
+    });
+    return hipGetLastError();
+}
+extern "C" hipError_t ctf_launch_obs_key_clear(const ObsShadow& shadow, int n_envs, hipStream_t st) {
+    hipLaunchKernelGGL(k_obs_key_clear, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, st, shadow.key, n_envs);
     return hipGetLastError();
 }
 extern "C" hipError_t ctf_launch_observe_codes(const DevCfg& cfg, const DevPtrs& p, uint8_t* codes, uint16_t* meta, uint16_t* selfcells,

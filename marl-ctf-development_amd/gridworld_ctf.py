@@ -61,6 +61,13 @@ class VecGridworldCtf:
     Env ``e`` reproduces, bit for bit, a reference process that ran
     ``random.seed(py_seeds[e]); np.random.seed(np_seeds[e])`` before constructing its env and was fed
     the same actions.  Outputs live in tensors owned by this object and are overwritten by the next call.
+
+    RETAINED OBSERVATIONS.  The observation buffer this object allocates itself (``obs``, on first use) is handed to the library
+    as retained (include/ctf_env.h, ctf_obs_retain): ``observe`` and ``step_observe`` then rewrite only the 128-byte lines of it
+    that changed since their last render.  The results are the same bytes — as long as nobody else writes into ``vec.obs``.
+    Whoever does (``vec.obs.fill_(...)``, a copy into it, another library) must call ``invalidate_obs()`` before the next
+    render.  A buffer assigned through ``vec.obs = buf`` is the caller's and is rendered in full every time.
+    ``observe_retained()`` says which of the two holds; CTF_OBS_RETAIN=0 in the environment switches retention off.
     """
 
     def __init__(self, n_envs, device=None, py_seeds=None, np_seeds=None, log_metrics=True, tune_placement=None, _lib=None,
@@ -123,11 +130,23 @@ class VecGridworldCtf:
                                     dtype=torch.uint8, device=self.device)
             if self._tune_placement:
                 self._tune_obs_placement()
+            # ours, and nobody writes it from here on (the search's last fill_ is behind us): retained
+            self._call("ctf_obs_retain", _abi.ptr(self._obs), self._stream())
         return self._obs
 
     @obs.setter
     def obs(self, buf):
+        self._call("ctf_obs_retain", None, self._stream())  # an assigned buffer is the caller's: rendered in full (also the search's probes)
         self._obs = buf
+
+    def invalidate_obs(self):
+        """Tell the library that somebody else has written into the retained ``obs``: the next render writes every byte.
+        Stream-ordered."""
+        self._call("ctf_obs_invalidate", self._stream())
+
+    def observe_retained(self):
+        """True when ``observe`` / ``step_observe`` rewrite only the changed lines of this object's buffer (the delta render)."""
+        return self._lib.ctf_observe_retained(self._h, _abi.ptr(self.obs)) == 1
 
     @property
     def codes(self):
