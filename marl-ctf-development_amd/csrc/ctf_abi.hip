@@ -45,6 +45,7 @@ struct ctf_env {
     uint8_t* retained;
     ObsShadow shadow;
     int delta_nt;       // CTF_OBS_DELTA_NT at retain: 0 / 1 force the delta render's store hint off / on, -1 = the full render's rule (store_hint)
+    int delta_bitmap;   // CTF_OBS_DELTA_BITMAP=1 at retain: the delta render is the round-11 kernel (the bitmap of the whole block)
 };
 
 // Layout of the ctf_host_step block (byte offsets; every segment 16-byte aligned, the observation 256-byte aligned).
@@ -142,6 +143,7 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     h->retained = nullptr;
     h->shadow = ObsShadow{nullptr, nullptr, nullptr};
     h->delta_nt = -1;
+    h->delta_bitmap = 0;
     {
         const char* ov = getenv("CTF_OBS_NT");
         h->nt_override = ov ? (atoi(ov) != 0) : -1;
@@ -367,7 +369,7 @@ extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t re
     if (!obs && !meta) return CTF_OK;
     DeviceScope guard(h->device);
     if (retained_here(h, obs)) {
-        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, (hipStream_t)stream));
         return CTF_OK;
     }
     h->d.obs_store_nt = store_hint(h);
@@ -403,6 +405,8 @@ extern "C" int ctf_obs_retain(ctf_env* h, uint8_t* obs, void* stream) {
     {
         const char* ov = getenv("CTF_OBS_DELTA_NT");
         h->delta_nt = ov ? (atoi(ov) != 0) : -1;
+        const char* bm = getenv("CTF_OBS_DELTA_BITMAP");
+        h->delta_bitmap = bm && atoi(bm) != 0;
     }
     // nothing is known about the buffer; the clear has landed before the call returns, so the first render may come on any stream
     HIP_TRY(ctf_launch_obs_key_clear(h->shadow, h->d.n_envs, (hipStream_t)stream));
@@ -459,7 +463,7 @@ extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, 
     }
     HIP_TRY(ctf_launch_step(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, 1, (hipStream_t)stream));
     if (retained_here(h, obs)) {
-        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, (hipStream_t)stream));
     } else if (obs || meta) {
         h->d.obs_store_nt = store_hint(h);
         HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, meta, reverse_mask), h->n_cus, (hipStream_t)stream));

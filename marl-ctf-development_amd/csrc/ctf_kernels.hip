@@ -19,6 +19,7 @@
 
 #include "ctf_launch.h"
 #include "ctf_obs_delta.h"
+#include "ctf_obs_chunk.h"
 // Profiling-only phase trace of the step kernel (tools/trace_step.py): lane 0 of every block stamps the 100 MHz wall clock at
 // fixed points (0 start, 1 staged, 7 hit bits, 5 ring, 6 shuffle 1, 8/9/10 + 3 k act / tagging / metrics of turn k, 32 turns
 // done, 33 shuffle 2, 34 stepped, 2 barrier, 3 written back, 4 end); never defined in the shipped build.
@@ -730,15 +731,17 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
 // State that changed behind the render (reset, auto-reset, set_state, import, restore) needs no notice: the shadow is compared
 // with the state itself.  Envs go to XCDs in contiguous eighths as in k_observe.
 // Per-wave LDS: [rec RS][mvals 96][meta staging][bitmap][line mask][line list u16].
+// This is the kernel of round 11, kept selectable (CTF_OBS_DELTA_BITMAP=1 at ctf_obs_retain) until k_observe_delta below has held
+// its numbers on more than one box.
 __host__ __device__ inline int delta_mask_bytes(int obs_bytes) { return ((obsd_lines(obs_bytes, CTF_OBS_LINE - 16) + 31) / 32 * 4 + 15) & ~15; }
 __host__ __device__ inline int delta_list_bytes(int obs_bytes) { return (obsd_lines(obs_bytes, CTF_OBS_LINE - 16) * 2 + 15) & ~15; }
-__host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int obs_bytes) {
+__host__ __device__ inline int delta_bitmap_wave_bytes(int RS, int N, int M, int obs_bytes) {
     return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_bitmap_bytes(obs_bytes) + delta_mask_bytes(obs_bytes) + delta_list_bytes(obs_bytes);
 }
 #define OBS_DELTA_UNROLL 4  // store instructions (of eight lines each) per pass, their bitmap halfwords read first
 
 template <int STORE_NT>
-__global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
+__global__ void __launch_bounds__(256) k_observe_delta_bitmap(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
                                                                      uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map) {
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x & (WAVE - 1);
@@ -748,7 +751,7 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
     const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
     if (e >= cfg.n_envs) return;  // (the whole wave: nothing below synchronises across waves)
-    uint8_t* wl = (uint8_t*)lds + wave * delta_wave_bytes(cfg.RS, N, M, OB);
+    uint8_t* wl = (uint8_t*)lds + wave * delta_bitmap_wave_bytes(cfg.RS, N, M, OB);
     uint8_t* srec = wl;
     uint16_t* mv = (uint16_t*)(wl + cfg.RS);
     uint16_t* mstage = (uint16_t*)(wl + cfg.RS + OBS_MV_BYTES);
@@ -854,6 +857,196 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     }
 
     // ---- 5. the shadow follows what the buffer now holds
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int w = lane + WAVE * j;
+        if (GW > WAVE * j && w < GW && (!known || cur[j] != old[j])) gsh[w] = cur[j];
+    }
+    if (lane < N && (!known || cur_pos != old_pos)) psh[lane] = (uint16_t)cur_pos;
+    if (!known && lane == 0) sh.key[e] = key;
+}
+// The same render without the block's bitmap (round 12; ctf_obs_chunk.h has the chunk rule).  The round-11 kernel is bound by the
+// vector ALU, not by a chain of latencies: while its waves are resident the SIMD's VALU is busy all the time (1 220 vector
+// instructions per wave, profiles/r12_delta_direct.md).  So this one issues fewer of them:
+//   - instead of one LDS OR per non-empty cell and VIEWING AGENT into N * CGG bits, one per cell and SLOT in use (viewer team x
+//     reversed: two for the default mask) into the slots' images of CGG bits each; a lane then takes its chunk's 16 bits from its
+//     view's slot image at bit (offset % CGG), ORs in the viewer's own cell and expands them (obsc_chunk_bits) — a first render
+//     (unknown key) goes the same way, every line being dirty;
+//   - the changed cells are first gathered into a list (ballot + lane count) and then marked one cell per lane, instead of every
+//     lane walking the four bytes of its dword in turn with the whole wave waiting on each;
+//   - the viewers' positions come from global memory with the other loads, so nothing waits for the record in LDS before the
+//     stores; the metadata rows (which need it) are made after the dirty lines' stores have been issued.
+// LDS operations of a wave complete in order, so the zeroing, the ORs and the mask's initialisation need no wait between them.
+// Per-wave LDS: [rec RS][mvals 96][meta staging][slot images 4 x][own cells u16[16]][changed cells u32[GS]][line mask][line list u16].
+__host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int CGG, int GS, int obs_bytes) {
+    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + 16 * obsc_image_dwords(CGG) + 2 * CTF_MAX_AGENTS + 4 * GS + delta_mask_bytes(obs_bytes) +
+           delta_list_bytes(obs_bytes);
+}
+
+#ifndef OBS_DELTA_META_FIRST
+#define OBS_DELTA_META_FIRST 0  // 1 = profiling comparison only: the metadata rows made before the dirty lines are marked and stored
+#endif
+
+template <int STORE_NT>
+__global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
+                                                       uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map) {
+    extern __shared__ uint32_t lds[];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4, IW = obsc_image_dwords(cfg.CGG);
+    const uint32_t b = blockIdx.x;
+    const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
+    const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
+    if (e >= cfg.n_envs) return;  // (the whole wave: nothing below synchronises across waves)
+    uint8_t* wl = (uint8_t*)lds + wave * delta_wave_bytes(cfg.RS, N, M, cfg.CGG, cfg.GS, OB);
+    uint8_t* srec = wl;
+    uint16_t* mv = (uint16_t*)(wl + cfg.RS);
+    uint16_t* mstage = (uint16_t*)(wl + cfg.RS + OBS_MV_BYTES);
+    uint32_t* images = (uint32_t*)(wl + cfg.RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M));
+    uint16_t* selfc = (uint16_t*)(images + 4 * IW);
+    uint32_t* chg = (uint32_t*)(selfc + CTF_MAX_AGENTS);
+    uint32_t* lmask = chg + cfg.GS;
+    uint16_t* llist = (uint16_t*)((uint8_t*)lmask + delta_mask_bytes(OB));
+
+    // ---- 1. loads, all issued before anything waits, on clamped indices
+    const uint32_t* gcur = (const uint32_t*)(p.grid + (size_t)e * cfg.GS);
+    uint32_t* gsh = (uint32_t*)(sh.grid + (size_t)e * cfg.GS);
+    const uint8_t* rec = p.rec + (size_t)e * cfg.RS;
+    const uint32_t recw = ((const uint32_t*)rec)[min(lane, cfg.RS / 4 - 1)];
+    const uint32_t cur_pos = *(const uint16_t*)(rec + cfg.off_pos + 2 * min(lane, N - 1));
+    uint32_t cur[4], old[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {  // G <= 32: at most 256 grid dwords (uniform conditions)
+        cur[j] = (GW > WAVE * j) ? gcur[min(lane + WAVE * j, GW - 1)] : 0u;
+        old[j] = (GW > WAVE * j) ? gsh[min(lane + WAVE * j, GW - 1)] : 0u;
+    }
+    uint16_t* psh = sh.pos + (size_t)e * CTF_MAX_AGENTS;
+    const uint32_t old_pos = psh[min(lane, N - 1)];
+    const uint32_t key = CTF_OBS_KEY(reverse_mask);
+    const bool known = sh.key[e] == key;  // uniform
+
+    ObsDeltaShape s;
+    s.N = N; s.G = cfg.G; s.GG = cfg.GG; s.CGG = cfg.CGG; s.obs_bytes = OB; s.flip_axis = cfg.flip_axis;
+    s.team_mask = cfg.team_mask; s.chan_lut[0] = cfg.chan_lut[0]; s.chan_lut[1] = cfg.chan_lut[1];
+    const uint32_t used = obsc_slots_used(s, reverse_mask);
+    const size_t base = (size_t)e * (size_t)OB;
+    const int lead = (int)(((uintptr_t)obs + base) & (uintptr_t)(CTF_OBS_LINE - 1));  // a multiple of 16
+    const int nl = obsd_lines(OB, lead), ndw = (nl + 31) >> 5;                       // ndw <= 64 (obsd_applies)
+
+    // ---- 2. everything the loaded registers give, into LDS: the slot images, the viewers' own cells, the mask's start, the
+    // list of changed cells
+    {
+        const u32x4_t z = {0u, 0u, 0u, 0u};
+        for (int q = lane; q < IW; q += WAVE) ((u32x4_t*)images)[q] = z;  // 4 images of IW dwords = IW x 16 bytes
+    }
+    if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
+    if (lane < ndw) {
+        const int left = nl - 32 * lane;
+        lmask[lane] = known ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
+    }
+    if (lane < N) selfc[lane] = (uint16_t)obsc_self_cell(s, reverse_mask, lane, (int)(int8_t)(cur_pos & 0xFFu), (int)(int8_t)(cur_pos >> 8));
+    int n_chg = 0;  // uniform
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int w = lane + WAVE * j;
+        if (GW > WAVE * j) {  // uniform
+            const bool mine = w < GW;
+            const uint32_t x = cur[j] ^ old[j];
+            int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - r * cfg.G;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int cell = 4 * w + q;
+                const bool in = mine && cell < cfg.GG;
+                if (in)
+                    obsc_build_cell(s, used, cell, r, c, (cur[j] >> (8 * q)) & 0xFFu,
+                                    [&](int slot, int bit) { atomicOr(images + slot * IW + (bit >> 5), 1u << (bit & 31)); });
+                if (++c == cfg.G) { c = 0; r++; }
+                if (known) {  // uniform
+                    const bool ch = in && ((x >> (8 * q)) & 0xFFu) != 0u;
+                    const uint64_t bal = __ballot(ch);
+                    if (bal) {  // uniform
+                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                        if (ch) chg[n_chg + (int)rank] = (uint32_t)cell | (((old[j] >> (8 * q)) & 0xFFu) << 16) | (((cur[j] >> (8 * q)) & 0xFFu) << 24);
+                        n_chg += __popcll(bal);
+                    }
+                }
+            }
+        }
+    }
+
+    const ObsSlots no_slots = {{0, 0, 0, 0}};
+    if (OBS_DELTA_META_FIRST && meta)
+        obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
+
+    // ---- 3. the dirty lines of the env's span: one changed cell per lane, then the viewers that moved
+    if (known) {
+        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+        __builtin_amdgcn_wave_barrier();
+        auto mark = [&](int line) {
+            if ((uint32_t)line < (uint32_t)nl) atomicOr(lmask + (line >> 5), 1u << (line & 31));
+        };
+        for (int at = 0; at < n_chg; at += WAVE) {
+            if (at + lane < n_chg) {
+                const uint32_t ent = chg[at + lane];
+                obsd_cell_changed(s, reverse_mask, lead, (int)(ent & 0xFFFFu), (ent >> 16) & 0xFFu, ent >> 24, mark);
+            }
+        }
+        if (lane < N && cur_pos != old_pos) {
+            const int oc = (int)(int8_t)(old_pos & 0xFFu) * cfg.G + (int)(int8_t)(old_pos >> 8);
+            const int nc = (int)(int8_t)(cur_pos & 0xFFu) * cfg.G + (int)(int8_t)(cur_pos >> 8);
+            obsd_viewer_moved(s, reverse_mask, lead, lane, oc, nc, mark);
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+    __builtin_amdgcn_wave_barrier();
+
+    // ---- 4. compact: lane q lists the set bits of mask dword q behind those of the dwords before it
+    uint32_t m = lane < ndw ? lmask[lane] : 0u;
+    int incl = __popc(m);
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int up = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += up;
+    }
+    const int total = __shfl(incl, WAVE - 1, WAVE);
+    for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
+    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+    __builtin_amdgcn_wave_barrier();
+    // ... and emit: lanes 8k .. 8k+7 hold the eight chunks of one line; chunks outside the env's own block belong to the
+    // neighbour's wave and are skipped (blocks are whole chunks)
+    {
+        uint8_t* out = obs + base;
+        const int sub = lane >> 3, off_in_line = (lane & 7) * 16 - lead;
+        for (int l0 = 0; l0 < total; l0 += 8 * OBS_DELTA_UNROLL) {
+            uint32_t h[OBS_DELTA_UNROLL];
+            int o[OBS_DELTA_UNROLL];
+#pragma unroll
+            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
+                const int idx = l0 + 8 * u + sub;
+                o[u] = idx < total ? (int)llist[idx] * CTF_OBS_LINE + off_in_line : -1;  // byte of the env's block
+                if (o[u] >= OB) o[u] = -1;
+                h[u] = 0u;
+                if (o[u] >= 0) {
+                    const int view = (int)fdiv((uint32_t)o[u], cfg.div_cgg);
+                    h[u] = obsc_chunk_bits(s, reverse_mask, images, IW, selfc, view, o[u] - view * cfg.CGG);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
+                if (o[u] >= 0) {
+                    const u32x4_t v = {obsc_expand4(h[u], 0), obsc_expand4(h[u], 1), obsc_expand4(h[u], 2), obsc_expand4(h[u], 3)};
+                    if (STORE_NT) __builtin_nontemporal_store(v, (u32x4_t*)(out + o[u]));
+                    else *(u32x4_t*)(out + o[u]) = v;
+                }
+            }
+        }
+    }
+
+    // ---- 5. the metadata rows, whole (obs_build_env parks the record in LDS and makes them from it)
+    if (!OBS_DELTA_META_FIRST && meta)
+        obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
+
+    // ---- 6. the shadow follows what the buffer now holds
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int w = lane + WAVE * j;
@@ -1465,17 +1658,23 @@ extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, co
 extern "C" int ctf_observe_delta_applies(const DevCfg& cfg, const uint8_t* obs) {
     return obs && ((uintptr_t)obs % 16) == 0 && obsd_applies(cfg.obs_bytes);
 }
-// k_observe_delta: one wave per env, up to 4 independent waves per block, a multiple of 8 blocks (XCD-contiguous envs)
+// k_observe_delta: one wave per env, up to 4 independent waves per block, a multiple of 8 blocks (XCD-contiguous envs);
+// bitmap != 0: the round-11 kernel (CTF_OBS_DELTA_BITMAP=1)
 extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs& p, const ObsShadow& shadow, const RenderArgs& r, int store_nt,
-                                               hipStream_t st) {
-    const int per_wave = delta_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes);
+                                               int bitmap, hipStream_t st) {
+    const int per_wave = bitmap ? delta_bitmap_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes)
+                                : delta_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.CGG, cfg.GS, cfg.obs_bytes);
     const int wpb = obs_waves_per_block(per_wave);
     const size_t sh = (size_t)wpb * per_wave;
     const unsigned blocks = (unsigned)(((cfg.n_envs + wpb - 1) / wpb + 7) / 8 * 8);
     const uint32_t xcd_map = obs_xcd_knob();
     with_bool(store_nt != 0, [&](auto NT) {
-        hipLaunchKernelGGL(k_observe_delta<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta, r.reverse_mask,
-                           xcd_map);
+        if (bitmap)
+            hipLaunchKernelGGL(k_observe_delta_bitmap<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta,
+                               r.reverse_mask, xcd_map);
+        else
+            hipLaunchKernelGGL(k_observe_delta<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta, r.reverse_mask,
+                               xcd_map);
     });
     return hipGetLastError();
 }

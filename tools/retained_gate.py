@@ -4,8 +4,10 @@ interleaved round by round as tools/ab_inproc.py does?
 
 Variants, all on the same handle and the same buffer (switched with ctf_obs_retain, so nothing else differs):
   full        the buffer released: k_observe_tiles rewrites all of it (what every render was before retention)
-  delta       the buffer retained, k_observe_delta with plain stores
+  delta       the buffer retained, the round-11 kernel (k_observe_delta_bitmap, CTF_OBS_DELTA_BITMAP=1) with plain stores
   delta-nt    the same with the nontemporal hint on its stores (CTF_OBS_DELTA_NT=1, read when the buffer is retained)
+  direct      the buffer retained, k_observe_delta (chunks from the slot images, no bitmap of the block) with plain stores
+  direct-nt   the same with the nontemporal hint
 Per round and variant: k_step and the render timed apart with events (the step of a variant runs behind that variant's render,
 so what the render leaves in the caches shows in it), then 100 back-to-back step_observe calls timed as one window.
 
@@ -49,7 +51,8 @@ def select(variant):
     if variant == "full":
         vec._call("ctf_obs_retain", None, vec._stream())
     else:
-        os.environ["CTF_OBS_DELTA_NT"] = "1" if variant == "delta-nt" else "0"
+        os.environ["CTF_OBS_DELTA_NT"] = "1" if variant.endswith("-nt") else "0"
+        os.environ["CTF_OBS_DELTA_BITMAP"] = "1" if variant.startswith("delta") else "0"
         vec._call("ctf_obs_retain", _abi.ptr(buf), vec._stream())
     assert vec.observe_retained() == (variant != "full")
     vec.observe()  # (after retaining: the one full pass that fills the shadow)
@@ -75,7 +78,7 @@ def window(reps=100):
     return st, ob, a.elapsed_time(b) / reps
 
 
-VARIANTS = ("full", "delta", "delta-nt")
+VARIANTS = ("full", "delta", "delta-nt", "direct", "direct-nt")
 for v in VARIANTS:
     select(v)
     window(30)
