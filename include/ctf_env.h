@@ -247,7 +247,9 @@ int32_t ctf_observe_stores_hinted(const ctf_env* env, const uint8_t* obs_dev);
  *   buffer per handle; a second call replaces the first; obs_dev = NULL releases it.  Retaining invalidates: the next render
  *   into the buffer writes everything.  The first call allocates the handle's SHADOW on the device — per env the grid and the
  *   position bytes the buffer's block was last rendered from, and one key word that names the reverse mask of that render or
- *   says "unknown" (about 270 bytes per arena env) — and the call waits for `stream` once (everything after it is capturable;
+ *   says "unknown", and the four slot images of that grid (CGG bits each: what a view shows apart from the viewer's own cell),
+ *   which a render carries forward from the cells that changed instead of rebuilding them; about 1 900 bytes per arena env,
+ *   1 600 of them the images: 123 MB at 65 536 envs against 18 MB before the images — and the call waits for `stream` once (everything after it is capturable;
  *   on a stream that is being captured the call retains nothing and renders stay full).  Renders into the retained buffer are then k_observe_delta: one wave per env compares the state with the shadow, and
  *   rewrites the dirty lines (all of them where the key is not the expected one) and the metadata rows.  Validity is device
  *   state only, so a hipGraph captured before the shadow was ever written replays correctly.  The delta render applies when
@@ -255,6 +257,9 @@ int32_t ctf_observe_stores_hinted(const ctf_env* env, const uint8_t* obs_dev);
  *   CTF_OBS_RETAIN=0 in the environment (read at the call), ctf_obs_retain is a no-op and renders stay full.
  *   CTF_STEP_OBSERVE_ONE_LAUNCH=1 wins over retention: that launch renders in full and invalidates.  The delta render's
  *   stores carry the nontemporal hint by the full render's rule (above); CTF_OBS_DELTA_NT=0 / 1 at the call forces it off / on.
+ *   Also read at the call and constant until the next one (so graph replays are unaffected): CTF_OBS_DELTA_REBUILD=1 (the slot
+ *   images are rebuilt from the grid at every render and the shadow's are never touched) and, for tests and soaks,
+ *   CTF_OBS_DELTA_ALL_DIRTY=1 (every line is rewritten at every render, the images still carried forward).
  * ctf_obs_invalidate: everything about the retained buffer is unknown again.  Stream-ordered, one small launch, capturable.
  * ctf_observe_retained: 1 if a ctf_observe into obs_dev would take the delta path now, else 0.
  * A render with obs_dev = NULL (metadata only) or into any other pointer leaves the shadow alone. */

@@ -20,6 +20,7 @@
 #include "ctf_device_scope.h"
 #include "ctf_harvest.h"
 #include "ctf_launch.h"
+#include "ctf_obs_chunk.h"
 #include "ctf_snapshot.h"
 #include "ctf_state_view.h"
 #include "ctf_states.h"
@@ -46,6 +47,7 @@ struct ctf_env {
     ObsShadow shadow;
     int delta_nt;       // CTF_OBS_DELTA_NT at retain: 0 / 1 force the delta render's store hint off / on, -1 = the full render's rule (store_hint)
     int delta_bitmap;   // CTF_OBS_DELTA_BITMAP=1 at retain: the delta render is the round-11 kernel (the bitmap of the whole block)
+    uint32_t delta_flags;  // CTF_OBS_DELTA_REBUILD / CTF_OBS_DELTA_ALL_DIRTY at retain: CTF_OBS_DELTA_F_* (ctf_device.h)
 };
 
 // Layout of the ctf_host_step block (byte offsets; every segment 16-byte aligned, the observation 256-byte aligned).
@@ -116,7 +118,7 @@ static void free_all(ctf_env* h) {
     (void)hipFree(h->p.rngctr); (void)hipFree(h->rng_scratch); (void)hipFree(h->p.rngready); (void)hipFree(h->p.rngage);
     (void)hipFree(h->p.py_top); (void)hipFree(h->p.np_hit); (void)hipFree(h->p.np_nib);
     (void)hipFree(h->sync);
-    (void)hipFree(h->shadow.grid); (void)hipFree(h->shadow.pos); (void)hipFree(h->shadow.key);
+    (void)hipFree(h->shadow.grid); (void)hipFree(h->shadow.pos); (void)hipFree(h->shadow.key); (void)hipFree(h->shadow.images);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     delete h;
 }
@@ -141,9 +143,10 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     h->hio_host = nullptr;
     h->sync = nullptr;
     h->retained = nullptr;
-    h->shadow = ObsShadow{nullptr, nullptr, nullptr};
+    h->shadow = ObsShadow{nullptr, nullptr, nullptr, nullptr};
     h->delta_nt = -1;
     h->delta_bitmap = 0;
+    h->delta_flags = 0u;
     {
         const char* ov = getenv("CTF_OBS_NT");
         h->nt_override = ov ? (atoi(ov) != 0) : -1;
@@ -369,7 +372,7 @@ extern "C" int ctf_observe(ctf_env* h, uint8_t* obs, uint16_t* meta, uint32_t re
     if (!obs && !meta) return CTF_OK;
     DeviceScope guard(h->device);
     if (retained_here(h, obs)) {
-        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, h->delta_flags, (hipStream_t)stream));
         return CTF_OK;
     }
     h->d.obs_store_nt = store_hint(h);
@@ -394,11 +397,13 @@ extern "C" int ctf_obs_retain(ctf_env* h, uint8_t* obs, void* stream) {
     }
     const size_t E = (size_t)h->d.n_envs;
     if (!h->shadow.key) {
-        ObsShadow s{nullptr, nullptr, nullptr};
+        ObsShadow s{nullptr, nullptr, nullptr, nullptr};
+        const size_t image_bytes = 16 * (size_t)obsc_image_dwords(h->d.CGG);  // four slot images per env
         if (hipMalloc((void**)&s.grid, E * h->d.GS) != hipSuccess || hipMalloc((void**)&s.pos, E * CTF_MAX_AGENTS * 2) != hipSuccess ||
-            hipMalloc((void**)&s.key, E * 4) != hipSuccess) {
-            (void)hipFree(s.grid); (void)hipFree(s.pos); (void)hipFree(s.key);
-            return fail(CTF_E_NOMEM, "ctf_obs_retain: hipMalloc of the shadow (%zu bytes) failed", E * ((size_t)h->d.GS + CTF_MAX_AGENTS * 2 + 4));
+            hipMalloc((void**)&s.key, E * 4) != hipSuccess || hipMalloc((void**)&s.images, E * image_bytes) != hipSuccess) {
+            (void)hipFree(s.grid); (void)hipFree(s.pos); (void)hipFree(s.key); (void)hipFree(s.images);
+            return fail(CTF_E_NOMEM, "ctf_obs_retain: hipMalloc of the shadow (%zu bytes) failed",
+                        E * ((size_t)h->d.GS + CTF_MAX_AGENTS * 2 + 4 + image_bytes));
         }
         h->shadow = s;
     }
@@ -407,6 +412,9 @@ extern "C" int ctf_obs_retain(ctf_env* h, uint8_t* obs, void* stream) {
         h->delta_nt = ov ? (atoi(ov) != 0) : -1;
         const char* bm = getenv("CTF_OBS_DELTA_BITMAP");
         h->delta_bitmap = bm && atoi(bm) != 0;
+        const char* rb = getenv("CTF_OBS_DELTA_REBUILD");
+        const char* ad = getenv("CTF_OBS_DELTA_ALL_DIRTY");
+        h->delta_flags = (rb && atoi(rb) != 0 ? CTF_OBS_DELTA_F_REBUILD : 0u) | (ad && atoi(ad) != 0 ? CTF_OBS_DELTA_F_ALL_DIRTY : 0u);
     }
     // nothing is known about the buffer; the clear has landed before the call returns, so the first render may come on any stream
     HIP_TRY(ctf_launch_obs_key_clear(h->shadow, h->d.n_envs, (hipStream_t)stream));
@@ -463,7 +471,7 @@ extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, 
     }
     HIP_TRY(ctf_launch_step(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, 1, (hipStream_t)stream));
     if (retained_here(h, obs)) {
-        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, h->delta_flags, (hipStream_t)stream));
     } else if (obs || meta) {
         h->d.obs_store_nt = store_hint(h);
         HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, meta, reverse_mask), h->n_cus, (hipStream_t)stream));

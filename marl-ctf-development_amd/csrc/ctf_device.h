@@ -112,12 +112,21 @@ struct DevPtrs {
 // The shadow of a handle's RETAINED observation buffer (ctf_obs_retain): what was last rendered into it — never a record of what
 // a step did.  Allocated at the first ctf_obs_retain.  key[e] == CTF_OBS_KEY(m) says "grid[e] / pos[e] are the state env e's
 // block of the retained buffer was rendered from, under reverse mask m"; anything else (0 after an invalidation) says nothing is
-// known about that block.  Only k_observe_delta reads and writes grid / pos; the key is also cleared by k_obs_key_clear.
+// known about that block.  Only k_observe_delta reads and writes grid / pos / images; the key is also cleared by k_obs_key_clear.
+// images[e] are env e's slot images (ctf_obs_chunk.h), kept so that a render carries them forward from the cells that changed
+// instead of rebuilding them from all cells: whenever key[e] == CTF_OBS_KEY(m), images[e] equals obsc_env_images(grid[e]) in the
+// slots in use under m (the other slots' dwords mean nothing).  They are derived from the shadow grid only — still no record of
+// what a step did — and written by the wave that writes that grid, in the same launch, so the key needs no second meaning.
+// 16 * obsc_image_dwords(CGG) bytes per env: 1 600 for the arena, against 256 + 32 + 4 for the rest of the shadow.
 struct ObsShadow {
-    uint8_t* grid;   // u8  [E][GS]
-    uint16_t* pos;   // u16 [E][CTF_MAX_AGENTS]: agent i's (row, col) bytes as the record holds them
-    uint32_t* key;   // u32 [E]
+    uint8_t* grid;     // u8  [E][GS]
+    uint16_t* pos;     // u16 [E][CTF_MAX_AGENTS]: agent i's (row, col) bytes as the record holds them
+    uint32_t* key;     // u32 [E]
+    uint32_t* images;  // u32 [E][4][obsc_image_dwords(CGG)]
 };
+// k_observe_delta's switches, read at ctf_obs_retain and constant for the handle's life
+#define CTF_OBS_DELTA_F_REBUILD 1u    // CTF_OBS_DELTA_REBUILD=1: the images are rebuilt from the grid at every render, the shadow's never touched
+#define CTF_OBS_DELTA_F_ALL_DIRTY 2u  // CTF_OBS_DELTA_ALL_DIRTY=1 (tests, soaks): every line is rewritten although the key is known
 #define CTF_OBS_KEY(reverse_mask) (0x80000000u | (uint32_t)(reverse_mask))
 
 // rec.misc[3]: bit 0 done, bit 1 base maps are implicitly zero (+1 at the start cells), bits 2.. = last step whose

@@ -877,6 +877,21 @@ __global__ void __launch_bounds__(256) k_observe_delta_bitmap(DevCfg cfg, DevPtr
 //   - the viewers' positions come from global memory with the other loads, so nothing waits for the record in LDS before the
 //     stores; the metadata rows (which need it) are made after the dirty lines' stores have been issued.
 // LDS operations of a wave complete in order, so the zeroing, the ORs and the mask's initialisation need no wait between them.
+// Round 13 takes out work the result does not need (profiles/r13_delta_images.md):
+//   - the slot images are a pure function of the grid the shadow already holds, so the shadow keeps them (ObsShadow.images) and a
+//     render with a known key loads them with its other loads, parks them in LDS and moves one bit per changed cell and slot
+//     (obsc_update_slot, a lane per (changed cell, slot)); the same lanes write the touched dwords back once the LDS operations
+//     have completed.  Two passes may touch one dword: the later pass's store carries the later value and a wave's stores to one
+//     address land in the order they were issued.  An unknown key (first render, invalidation, mask change) builds the images
+//     from all cells as before and writes the slots in use to the shadow whole.  REBUILD (CTF_OBS_DELTA_REBUILD=1) is round 12's
+//     behaviour: built at every render, the shadow's images neither read nor written;
+//   - the dirty lines are marked by one lane per (changed cell, viewer) pair (obsd_pair_changed_at) instead of one lane per cell
+//     walking teams and viewers in a scalar loop on a nearly empty wave: 0.015 of the 0.020 ms the round takes off step + render
+//     (0.177 -> 0.156 ms; the carried images give 0.002).
+// (Compacting the mask 64 lines per pass with the mask's dwords as ballots, in place of the scan and the per-lane bit loop of
+// step 4, was built and measured too: it lost 0.005 ms and is not here.)
+// `all_dirty` (CTF_OBS_DELTA_ALL_DIRTY=1, tests and soaks): every line is rewritten although the key is known, the images still
+// carried forward — every byte of the buffer then shows what the retained images hold.
 // Per-wave LDS: [rec RS][mvals 96][meta staging][slot images 4 x][own cells u16[16]][changed cells u32[GS]][line mask][line list u16].
 __host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int CGG, int GS, int obs_bytes) {
     return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + 16 * obsc_image_dwords(CGG) + 2 * CTF_MAX_AGENTS + 4 * GS + delta_mask_bytes(obs_bytes) +
@@ -887,13 +902,15 @@ __host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int CGG, i
 #define OBS_DELTA_META_FIRST 0  // 1 = profiling comparison only: the metadata rows made before the dirty lines are marked and stored
 #endif
 
-template <int STORE_NT>
+#define OBS_DELTA_IMG_REGS 2  // 16-byte units of the shadow's images a lane loads with the first loads (the arena needs one)
+
+template <int STORE_NT, bool REBUILD>
 __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
-                                                       uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map) {
+                                                       uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map, uint32_t all_dirty) {
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4, IW = obsc_image_dwords(cfg.CGG);
+    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4, IW = obsc_image_dwords(cfg.CGG), IU = IW / 4;
     const uint32_t b = blockIdx.x;
     const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
     const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
@@ -932,41 +949,76 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     const size_t base = (size_t)e * (size_t)OB;
     const int lead = (int)(((uintptr_t)obs + base) & (uintptr_t)(CTF_OBS_LINE - 1));  // a multiple of 16
     const int nl = obsd_lines(OB, lead), ndw = (nl + 31) >> 5;                       // ndw <= 64 (obsd_applies)
+    // the shadow's images of the slots in use, 16 bytes per lane: unit q of [rank of the slot among those in use][IU] is unit
+    // slot * IU + u of the env's [4][IU]
+    uint32_t* ish = sh.images + (size_t)e * (size_t)(4 * IW);
+    uint32_t slot_of_rank = 0u;  // nibble k = the k-th slot in use
+    int n_iu = 0;
+    for (int sl = 0; sl < 4; sl++)
+        if (used & (1u << sl)) { slot_of_rank |= (uint32_t)sl << (4 * n_iu); n_iu++; }
+    n_iu *= IU;
+    auto image_unit = [&](int q) {
+        const int k = (q >= IU) + (q >= 2 * IU) + (q >= 3 * IU);
+        return q + ((int)((slot_of_rank >> (4 * k)) & 3u) - k) * IU;
+    };
+    u32x4_t img[OBS_DELTA_IMG_REGS];
+    if (!REBUILD) {
+#pragma unroll
+        for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
+            if (n_iu > WAVE * j) img[j] = ((const u32x4_t*)ish)[image_unit(min(lane + WAVE * j, n_iu - 1))];  // (uniform condition)
+    }
+    const bool build = REBUILD || !known;  // uniform
 
     // ---- 2. everything the loaded registers give, into LDS: the slot images, the viewers' own cells, the mask's start, the
     // list of changed cells
-    {
+    if (build) {
         const u32x4_t z = {0u, 0u, 0u, 0u};
         for (int q = lane; q < IW; q += WAVE) ((u32x4_t*)images)[q] = z;  // 4 images of IW dwords = IW x 16 bytes
+    } else if (!REBUILD) {
+#pragma unroll
+        for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
+            if (lane + WAVE * j < n_iu) ((u32x4_t*)images)[image_unit(lane + WAVE * j)] = img[j];
+        for (int q = lane + WAVE * OBS_DELTA_IMG_REGS; q < n_iu; q += WAVE)  // larger shapes: the rest, loaded here
+            ((u32x4_t*)images)[image_unit(q)] = ((const u32x4_t*)ish)[image_unit(q)];
     }
     if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
     if (lane < ndw) {
         const int left = nl - 32 * lane;
-        lmask[lane] = known ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
+        lmask[lane] = (known && !all_dirty) ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
     }
     if (lane < N) selfc[lane] = (uint16_t)obsc_self_cell(s, reverse_mask, lane, (int)(int8_t)(cur_pos & 0xFFu), (int)(int8_t)(cur_pos >> 8));
+    if (build) {  // from all cells
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int w = lane + WAVE * j;
+            if (GW > WAVE * j) {  // uniform
+                const bool mine = w < GW;
+                int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - r * cfg.G;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int cell = 4 * w + q;
+                    if (mine && cell < cfg.GG)
+                        obsc_build_cell(s, used, cell, r, c, (cur[j] >> (8 * q)) & 0xFFu,
+                                        [&](int slot, int bit) { atomicOr(images + slot * IW + (bit >> 5), 1u << (bit & 31)); });
+                    if (++c == cfg.G) { c = 0; r++; }
+                }
+            }
+        }
+    }
     int n_chg = 0;  // uniform
+    if (known) {    // the changed cells, gathered: cell | old tile << 16 | new tile << 24
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int w = lane + WAVE * j;
-        if (GW > WAVE * j) {  // uniform
-            const bool mine = w < GW;
+        for (int j = 0; j < 4; j++) {
+            const int w = lane + WAVE * j;
             const uint32_t x = cur[j] ^ old[j];
-            int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - r * cfg.G;
+            if (GW > WAVE * j && __ballot(w < GW && x != 0u)) {  // uniform
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int cell = 4 * w + q;
-                const bool in = mine && cell < cfg.GG;
-                if (in)
-                    obsc_build_cell(s, used, cell, r, c, (cur[j] >> (8 * q)) & 0xFFu,
-                                    [&](int slot, int bit) { atomicOr(images + slot * IW + (bit >> 5), 1u << (bit & 31)); });
-                if (++c == cfg.G) { c = 0; r++; }
-                if (known) {  // uniform
-                    const bool ch = in && ((x >> (8 * q)) & 0xFFu) != 0u;
+                for (int q = 0; q < 4; q++) {
+                    const int cell = 4 * w + q;
+                    const bool ch = w < GW && cell < cfg.GG && ((x >> (8 * q)) & 0xFFu) != 0u;
                     const uint64_t bal = __ballot(ch);
                     if (bal) {  // uniform
-                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                        if (ch) chg[n_chg + (int)rank] = (uint32_t)cell | (((old[j] >> (8 * q)) & 0xFFu) << 16) | (((cur[j] >> (8 * q)) & 0xFFu) << 24);
+                        if (ch) chg[n_chg + obsd_rank(bal, lane)] = (uint32_t)cell | (((old[j] >> (8 * q)) & 0xFFu) << 16) | (((cur[j] >> (8 * q)) & 0xFFu) << 24);
                         n_chg += __popcll(bal);
                     }
                 }
@@ -985,16 +1037,39 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
         auto mark = [&](int line) {
             if ((uint32_t)line < (uint32_t)nl) atomicOr(lmask + (line >> 5), 1u << (line & 31));
         };
-        for (int at = 0; at < n_chg; at += WAVE) {
-            if (at + lane < n_chg) {
-                const uint32_t ent = chg[at + lane];
-                obsd_cell_changed(s, reverse_mask, lead, (int)(ent & 0xFFFFu), (ent >> 16) & 0xFFu, ent >> 24, mark);
+        // a lane per (changed cell, viewer): viewers padded to a power of two, so a pair's cell and viewer are a shift and a mask
+        const int vsh = N > 1 ? 32 - __clz(N - 1) : 0, n_pairs = n_chg << vsh;
+        for (int at = 0; at < n_pairs; at += WAVE) {
+            const int ci = (at + lane) >> vsh, i = (at + lane) & ((1 << vsh) - 1);
+            if (ci < n_chg && i < N) {
+                const uint32_t ent = chg[ci];
+                const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
+                obsd_pair_changed_at(s, lead, ((reverse_mask >> i) & 1u) ? obsc_flip_rc(s, cell, r, cell - r * cfg.G) : cell, i, (ent >> 16) & 0xFFu,
+                                     ent >> 24, mark);
             }
         }
         if (lane < N && cur_pos != old_pos) {
             const int oc = (int)(int8_t)(old_pos & 0xFFu) * cfg.G + (int)(int8_t)(old_pos >> 8);
             const int nc = (int)(int8_t)(cur_pos & 0xFFu) * cfg.G + (int)(int8_t)(cur_pos >> 8);
             obsd_viewer_moved(s, reverse_mask, lead, lane, oc, nc, mark);
+        }
+        if (!REBUILD) {
+            // the images follow the grid: a lane per (changed cell, slot) moves its bit, then stores the dwords it touched
+            for (int at = 0; at < 4 * n_chg; at += WAVE) {
+                const int ci = (at + lane) >> 2, slot = (at + lane) & 3;
+                int w_clear = -1, w_set = -1;
+                if (ci < n_chg && (used & (1u << slot))) {
+                    const uint32_t ent = chg[ci];
+                    const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
+                    obsc_update_slot(s, slot, cell, r, cell - r * cfg.G, (ent >> 16) & 0xFFu, ent >> 24,
+                                     [&](int sl, int bit) { w_clear = sl * IW + (bit >> 5); atomicAnd(images + w_clear, ~(1u << (bit & 31))); },
+                                     [&](int sl, int bit) { w_set = sl * IW + (bit >> 5); atomicOr(images + w_set, 1u << (bit & 31)); });
+                }
+                __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+                __builtin_amdgcn_wave_barrier();
+                if (w_clear >= 0) ish[w_clear] = images[w_clear];
+                if (w_set >= 0) ish[w_set] = images[w_set];
+            }
         }
     }
     __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
@@ -1053,6 +1128,8 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
         if (GW > WAVE * j && w < GW && (!known || cur[j] != old[j])) gsh[w] = cur[j];
     }
     if (lane < N && (!known || cur_pos != old_pos)) psh[lane] = (uint16_t)cur_pos;
+    if (!REBUILD && !known)  // the images built from all cells: the slots in use, whole
+        for (int q = lane; q < n_iu; q += WAVE) ((u32x4_t*)ish)[image_unit(q)] = ((const u32x4_t*)images)[image_unit(q)];
     if (!known && lane == 0) sh.key[e] = key;
 }
 // Everything about the retained buffer is unknown again (ctf_obs_invalidate; behind every other launch that writes the buffer)
@@ -1661,7 +1738,7 @@ extern "C" int ctf_observe_delta_applies(const DevCfg& cfg, const uint8_t* obs) 
 // k_observe_delta: one wave per env, up to 4 independent waves per block, a multiple of 8 blocks (XCD-contiguous envs);
 // bitmap != 0: the round-11 kernel (CTF_OBS_DELTA_BITMAP=1)
 extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs& p, const ObsShadow& shadow, const RenderArgs& r, int store_nt,
-                                               int bitmap, hipStream_t st) {
+                                               int bitmap, uint32_t flags, hipStream_t st) {
     const int per_wave = bitmap ? delta_bitmap_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes)
                                 : delta_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.CGG, cfg.GS, cfg.obs_bytes);
     const int wpb = obs_waves_per_block(per_wave);
@@ -1673,8 +1750,10 @@ extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs&
             hipLaunchKernelGGL(k_observe_delta_bitmap<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta,
                                r.reverse_mask, xcd_map);
         else
-            hipLaunchKernelGGL(k_observe_delta<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta, r.reverse_mask,
-                               xcd_map);
+            with_bool((flags & CTF_OBS_DELTA_F_REBUILD) != 0u, [&](auto RB) {
+                hipLaunchKernelGGL((k_observe_delta<NT.value, RB.value>), dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta,
+                                   r.reverse_mask, xcd_map, (flags & CTF_OBS_DELTA_F_ALL_DIRTY) ? 1u : 0u);
+            });
     });
     return hipGetLastError();
 }

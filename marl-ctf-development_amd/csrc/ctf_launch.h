@@ -39,7 +39,7 @@ hipError_t ctf_launch_observe_codes(const DevCfg&, const DevPtrs&, uint8_t* code
                                     int n_cus, hipStream_t);
 hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t* metrics, int32_t* captures, int32_t* steps, hipStream_t);
 hipError_t ctf_launch_random_actions(const DevCfg&, int8_t* actions, uint64_t seed, uint32_t step, uint32_t env_offset, hipStream_t);
-hipError_t ctf_launch_observe_delta(const DevCfg&, const DevPtrs&, const ObsShadow&, const RenderArgs&, int store_nt, int bitmap, hipStream_t);
+hipError_t ctf_launch_observe_delta(const DevCfg&, const DevPtrs&, const ObsShadow&, const RenderArgs&, int store_nt, int bitmap, uint32_t flags, hipStream_t);
 hipError_t ctf_launch_obs_key_clear(const ObsShadow&, int n_envs, hipStream_t);
 int ctf_observe_delta_applies(const DevCfg&, const uint8_t* obs);    // 1: a retained `obs` can take k_observe_delta
 int ctf_step_blocks(const DevCfg&);                                // step blocks of a step launch

@@ -13,6 +13,8 @@
 // from bit r = o % CGG of its view's slot image with one funnel shift, ORs in the viewer's own cell and expands every bit to a
 // byte.  A view's planes are contiguous in its image as they are in the block, so only a chunk that runs from one VIEW into the
 // next (CGG is rarely a multiple of 16) is made of two segments, each from its own view's image.
+// The images depend on the grid alone, so the handle's shadow keeps them between renders (ObsShadow.images, ctf_device.h) and a
+// render moves one bit per changed cell and slot (obsc_update_slot) instead of building them again.
 //
 // Compiled for the device by ctf_kernels.hip and for the host by tests/obs_chunk/ (checked against the oracle's renders without a
 // GPU), in the manner of ctf_obs_delta.h.  The host's obsc_chunk is the rule spelled out byte by byte; obsc_chunk_images goes through
@@ -31,9 +33,8 @@ OBSC_FN int obsc_slot(const ObsDeltaShape& s, uint32_t reverse_mask, int i) {
 }
 // which slots some agent looks through (bit per slot)
 OBSC_FN uint32_t obsc_slots_used(const ObsDeltaShape& s, uint32_t reverse_mask) {
-    uint32_t used = 0;
-    for (int i = 0; i < s.N; i++) used |= 1u << obsc_slot(s, reverse_mask, i);
-    return used;
+    const uint32_t all = (1u << s.N) - 1u, t = s.team_mask & all, rv = reverse_mask & all;  // N <= 16
+    return ((all & ~t & ~rv) ? 1u : 0u) | ((~t & rv) ? 2u : 0u) | ((t & ~rv) ? 4u : 0u) | ((t & rv) ? 8u : 0u);
 }
 // dwords of one slot's image: CGG bits, one dword more for the second half of the last funnel read, in whole 16-byte units
 OBSC_FN int obsc_image_dwords(int CGG) { return (((CGG + 31) >> 5) + 1 + 3) & ~3; }
@@ -65,6 +66,25 @@ OBSC_FN void obsc_build_cell(const ObsDeltaShape& s, uint32_t used, int cell, in
         if (used & (1u << (2 * t))) set(2 * t, (int)code * s.GG + cell);
         if (used & (2u << (2 * t))) set(2 * t + 1, (int)code * s.GG + fl);
     }
+}
+
+// The images carried forward instead of rebuilt: `cell` (row r, column c) went from tile a to tile b.  In one slot's image the
+// old tile's bit goes and the new tile's bit comes — clear(slot, bit), set(slot, bit); nothing for the empty tile, a tile without a
+// plane, or two tiles the slot's team sees in the same plane.  Images that equalled obsc_env_images of the old grid equal those of
+// the new grid once every changed cell has been through this (a cell owns its bit positions: no two cells touch the same bit).
+template <class Clear, class Set>
+OBSC_FN void obsc_update_slot(const ObsDeltaShape& s, int slot, int cell, int r, int c, uint32_t a, uint32_t b, Clear clear, Set set) {
+    const uint32_t ca = a ? obsd_channel(s, slot >> 1, a) : CTF_OBS_CODE_NONE, cb = b ? obsd_channel(s, slot >> 1, b) : CTF_OBS_CODE_NONE;
+    if (ca == cb) return;
+    const int at = (slot & 1) ? obsc_flip_rc(s, cell, r, c) : cell;
+    if (ca != CTF_OBS_CODE_NONE) clear(slot, (int)ca * s.GG + at);
+    if (cb != CTF_OBS_CODE_NONE) set(slot, (int)cb * s.GG + at);
+}
+// ... in every slot in `used` (k_observe_delta gives every (changed cell, slot) its own lane)
+template <class Clear, class Set>
+OBSC_FN void obsc_update_cell(const ObsDeltaShape& s, uint32_t used, int cell, int r, int c, uint32_t a, uint32_t b, Clear clear, Set set) {
+    for (int slot = 0; slot < 4; slot++)
+        if (used & (1u << slot)) obsc_update_slot(s, slot, cell, r, c, a, b, clear, set);
 }
 
 // 16 bits of view i from its byte r on: its slot's image, and its own cell in plane 0.  Bits from CGG - r on are not the view's.

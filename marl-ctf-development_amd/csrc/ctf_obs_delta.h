@@ -46,7 +46,7 @@ OBSD_FN bool obsd_applies(int obs_bytes) {
 
 // the render's own lookup (obs_build_env): nibble v of the 64-bit LUT
 OBSD_FN uint32_t obsd_channel(const ObsDeltaShape& s, int team, uint32_t v) {
-    const uint64_t lut = s.chan_lut[team];
+    const uint64_t lut = team ? s.chan_lut[1] : s.chan_lut[0];  // (a select: `team` may differ from lane to lane on the device)
     return (((v & 8u) ? (uint32_t)(lut >> 32) : (uint32_t)lut) >> (4u * (v & 7u))) & 15u;
 }
 
@@ -75,6 +75,23 @@ OBSD_FN void obsd_cell_changed(const ObsDeltaShape& s, uint32_t reverse_mask, in
     }
 }
 
+// The same rule for one (changed cell, viewer) PAIR — what a lane of k_observe_delta does, the pairs of an env spread over the
+// wave: viewer i's two bytes.  The union of the marks over i = 0 .. N-1 is obsd_cell_changed's.  `shown` is the cell as viewer
+// i's view shows it (the kernel has the cell's row and column at hand and flips without a division).
+template <class Mark>
+OBSD_FN void obsd_pair_changed_at(const ObsDeltaShape& s, int lead, int shown, int i, uint32_t a, uint32_t b, Mark mark) {
+    const int t = (int)((s.team_mask >> i) & 1u);
+    const uint32_t ca = obsd_channel(s, t, a), cb = obsd_channel(s, t, b);
+    if (ca == cb) return;
+    const int at = lead + i * s.CGG + shown;
+    if (ca != 15u) mark((at + (int)ca * s.GG) >> CTF_OBS_LINE_SHIFT);
+    if (cb != 15u) mark((at + (int)cb * s.GG) >> CTF_OBS_LINE_SHIFT);
+}
+template <class Mark>
+OBSD_FN void obsd_pair_changed(const ObsDeltaShape& s, uint32_t reverse_mask, int lead, int cell, int i, uint32_t a, uint32_t b, Mark mark) {
+    obsd_pair_changed_at(s, lead, ((reverse_mask >> i) & 1u) ? obsd_flip(s, cell) : cell, i, a, b, mark);
+}
+
 // viewer i moved from old_cell to new_cell (old_cell != new_cell): the two bytes of its plane 0
 template <class Mark>
 OBSD_FN void obsd_viewer_moved(const ObsDeltaShape& s, uint32_t reverse_mask, int lead, int i, int old_cell, int new_cell, Mark mark) {
@@ -82,6 +99,18 @@ OBSD_FN void obsd_viewer_moved(const ObsDeltaShape& s, uint32_t reverse_mask, in
     const int at = lead + i * s.CGG;
     mark((at + (rev ? obsd_flip(s, old_cell) : old_cell)) >> CTF_OBS_LINE_SHIFT);
     mark((at + (rev ? obsd_flip(s, new_cell) : new_cell)) >> CTF_OBS_LINE_SHIFT);
+}
+
+// A wave's ballot made into an ascending list, 64 items per pass (k_observe_delta gathers the changed cells so): in pass p lane L
+// stands for item 64p + L, `bal` holds bit L = the item is in, and such a lane writes its item at list[base + obsd_rank(bal, L)],
+// base = the popcounts of the earlier passes' ballots.
+OBSD_FN int obsd_rank(uint64_t bal, int lane) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lane;  // the executing lane: the hardware's count of the set bits below it
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+#else
+    return __builtin_popcountll(bal & ((1ull << lane) - 1ull));
+#endif
 }
 
 #if !defined(__HIPCC__)

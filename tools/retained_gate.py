@@ -6,12 +6,15 @@ Variants, all on the same handle and the same buffer (switched with ctf_obs_reta
   full        the buffer released: k_observe_tiles rewrites all of it (what every render was before retention)
   delta       the buffer retained, the round-11 kernel (k_observe_delta_bitmap, CTF_OBS_DELTA_BITMAP=1) with plain stores
   delta-nt    the same with the nontemporal hint on its stores (CTF_OBS_DELTA_NT=1, read when the buffer is retained)
-  direct      the buffer retained, k_observe_delta (chunks from the slot images, no bitmap of the block) with plain stores
+  rebuild     the buffer retained, k_observe_delta as round 12 had it: the slot images rebuilt from the grid at every render
+              (CTF_OBS_DELTA_REBUILD=1), plain stores
+  rebuild-nt  the same with the nontemporal hint
+  direct      the buffer retained, k_observe_delta with the slot images kept in the shadow and carried forward, plain stores
   direct-nt   the same with the nontemporal hint
 Per round and variant: k_step and the render timed apart with events (the step of a variant runs behind that variant's render,
 so what the render leaves in the caches shows in it), then 100 back-to-back step_observe calls timed as one window.
 
-Usage: python tools/retained_gate.py [envs] [arena|arena20|split] [rounds]      (prints a markdown table)"""
+Usage: python tools/retained_gate.py [envs] [arena|arena20|split] [rounds] [variant,variant,...]      (prints a markdown table)"""
 import importlib
 import os
 import sys
@@ -53,6 +56,7 @@ def select(variant):
     else:
         os.environ["CTF_OBS_DELTA_NT"] = "1" if variant.endswith("-nt") else "0"
         os.environ["CTF_OBS_DELTA_BITMAP"] = "1" if variant.startswith("delta") else "0"
+        os.environ["CTF_OBS_DELTA_REBUILD"] = "1" if variant.startswith("rebuild") else "0"
         vec._call("ctf_obs_retain", _abi.ptr(buf), vec._stream())
     assert vec.observe_retained() == (variant != "full")
     vec.observe()  # (after retaining: the one full pass that fills the shadow)
@@ -78,7 +82,10 @@ def window(reps=100):
     return st, ob, a.elapsed_time(b) / reps
 
 
-VARIANTS = ("full", "delta", "delta-nt", "direct", "direct-nt")
+VARIANTS = ("full", "delta", "delta-nt", "rebuild", "rebuild-nt", "direct", "direct-nt")
+if len(sys.argv) > 4:
+    assert set(sys.argv[4].split(",")) <= set(VARIANTS), sys.argv[4]
+    VARIANTS = tuple(sys.argv[4].split(","))
 for v in VARIANTS:
     select(v)
     window(30)
