@@ -68,6 +68,9 @@ extern "C" {
                              seed, counter = (n / 4, stream, "CTF1"))[n % 4]; the draws are made from those words by the
                              reference's own rules (random.shuffle, np.random.rand, np.random.randint): a reference run
                              whose three functions read the same tape gives the same trajectory                     */
+#define CTF_RNG_COUNTER_DIRECT 2 /* the same tape and the same three draw rules as CTF_RNG_COUNTER, so the same trajectory for
+                             the same seeds — but no generator words are stored; per env the state is the two seeds and the
+                             two counts of words consumed (32 bytes), and the step computes the Philox blocks it draws from */
 
 /* ctf_step flags */
 #define CTF_STEP_AUTO_RESET 1u /* an env whose `done` is set is reset before it is stepped (not in the
@@ -108,7 +111,7 @@ typedef struct ctf_config {
     int32_t drop_flag_when_no_hp; /* DROP_FLAG_WHEN_NO_HP (:64)                                 */
     int32_t log_metrics;          /* 1 = keep counters + visitation maps (always on in the reference) */
     int32_t n_opponents[2];       /* len(OPPONENTS[t]) (:392-395)                               */
-    int32_t rng_mode;             /* CTF_RNG_MT19937 (the reference's generators) or CTF_RNG_COUNTER */
+    int32_t rng_mode;             /* CTF_RNG_MT19937 (the reference's generators), CTF_RNG_COUNTER or CTF_RNG_COUNTER_DIRECT */
     int32_t reserved0[5];         /* keeps the doubles 8-byte aligned without implicit padding */
 
     double heal_per_step;         /* AGENT_HP_HEALING_PER_STEP (:212)                           */

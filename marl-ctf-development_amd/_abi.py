@@ -28,6 +28,7 @@ HARVEST_ALL = 1
 HARVEST_HEAD = 8  # words of a harvest row before the counters (include/ctf_env.h, ctf_harvest_episodes)
 RNG_MT19937 = 0
 RNG_COUNTER = 1
+RNG_COUNTER_DIRECT = 2  # the tape of RNG_COUNTER with nothing stored: 32 bytes of RNG state per env
 REVERSE_DEFAULT = 0xFFFFFFFF
 
 # order of ctf_state_view.metrics rows == the reference's "agent_*" metric names (gridworld_ctf.py:456-468)

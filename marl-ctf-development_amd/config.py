@@ -78,7 +78,8 @@ def opponents_of(agent_teams):
 
 def build_config(kwargs, log_metrics=True, rng_mode=0):
     """-> (CtfConfig, derived) where ``derived`` holds the host-side attributes of the reference env.
-    ``rng_mode``: _abi.RNG_MT19937 (the reference's two generators, default) or _abi.RNG_COUNTER (include/ctf_env.h)."""
+    ``rng_mode``: _abi.RNG_MT19937 (the reference's two generators, default), _abi.RNG_COUNTER or _abi.RNG_COUNTER_DIRECT
+    (include/ctf_env.h)."""
     kw = dict(DEFAULT_KWARGS)
     unknown = set(kwargs) - set(kw)
     if unknown:

@@ -168,15 +168,17 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     if (hipMalloc((void**)&(ptr), (bytes)) != hipSuccess) { free_all(h); return fail(CTF_E_NOMEM, "hipMalloc(%zu) failed", (size_t)(bytes)); }
     ALLOC(h->p.grid, E * d.GS);
     ALLOC(h->p.rec, E * d.RS);
-    ALLOC(h->p.mt_py, E * 2 * CTF_MT_N * 4);
-    ALLOC(h->p.mt_np, E * 2 * CTF_MT_N * 4);
-    ALLOC(h->p.py_top, E * 2 * CTF_P8_DW * 4);
-    ALLOC(h->p.np_hit, E * 2 * CTF_HB_DW * 4);
-    ALLOC(h->p.np_nib, E * 2 * CTF_NB_DW * 4);
-    ALLOC(h->p.rngpos, E * 2 * 4);
-    ALLOC(h->p.rngready, E * 2);
-    ALLOC(h->p.rngage, E * 2);
-    ALLOC(h->p.rngctr, (d.rng_mode == CTF_RNG_COUNTER ? E * 6 : 1) * 8);
+    const bool direct = d.rng_mode == CTF_RNG_COUNTER_DIRECT;  // no rings, digests, positions or flags: placeholders that nothing touches
+    const size_t RE = direct ? 0 : E;                          // envs that own rings
+    ALLOC(h->p.mt_py, RE ? RE * 2 * CTF_MT_N * 4 : 4);
+    ALLOC(h->p.mt_np, RE ? RE * 2 * CTF_MT_N * 4 : 4);
+    ALLOC(h->p.py_top, RE ? RE * 2 * CTF_P8_DW * 4 : 4);
+    ALLOC(h->p.np_hit, RE ? RE * 2 * CTF_HB_DW * 4 : 4);
+    ALLOC(h->p.np_nib, RE ? RE * 2 * CTF_NB_DW * 4 : 4);
+    ALLOC(h->p.rngpos, RE ? RE * 2 * 4 : 4);
+    ALLOC(h->p.rngready, RE ? RE * 2 : 1);
+    ALLOC(h->p.rngage, RE ? RE * 2 : 1);
+    ALLOC(h->p.rngctr, (d.rng_mode == CTF_RNG_COUNTER ? E * 6 : (direct ? E * 4 : 1)) * 8);
     ALLOC(h->rng_scratch, 2 * (CTF_MT_N + 1) * 4);
     ALLOC(h->p.metrics, met_elems * 4);
     ALLOC(h->p.vis, vis_elems * 4);
@@ -201,8 +203,8 @@ extern "C" int ctf_create(const ctf_config* cfg, int32_t n_envs, int32_t device_
     hipError_t e4 = ctf_launch_reset(h->d, h->p, nullptr, 1, nullptr);
     hipError_t e5 = hipMemset(h->seed_scratch, 0, E * 2 * 8);
     hipError_t e6 = ctf_launch_seed(h->d, h->p, h->seed_scratch, h->seed_scratch + E, nullptr);
-    if (e6 == hipSuccess) e6 = ctf_launch_rng_refill(h->d, h->p, 0, n_envs, 1, nullptr);
-    if (e6 == hipSuccess) e6 = hipMemset(h->p.rngage, 0, E * 2);  // (a seed / state import leaves every ring in place: the ages go back to 0 by themselves, tail_block)
+    if (e6 == hipSuccess && !direct) e6 = ctf_launch_rng_refill(h->d, h->p, 0, n_envs, 1, nullptr);
+    if (e6 == hipSuccess && !direct) e6 = hipMemset(h->p.rngage, 0, E * 2);  // (a seed / state import leaves every ring in place: the ages go back to 0 by themselves, tail_block)
     hipError_t e7 = hipDeviceSynchronize();
     if (e4 != hipSuccess || e5 != hipSuccess || e6 != hipSuccess || e7 != hipSuccess) {
         const hipError_t bad = e4 != hipSuccess ? e4 : e5 != hipSuccess ? e5 : e6 != hipSuccess ? e6 : e7;
@@ -241,21 +243,25 @@ extern "C" int ctf_seed(ctf_env* h, const uint64_t* py_seeds, const uint64_t* np
     HIP_TRY(hipMemcpyAsync(h->seed_scratch, py_seeds, E * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->seed_scratch + E, np_seeds, E * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(ctf_launch_seed(h->d, h->p, h->seed_scratch, h->seed_scratch + E, st));
-    HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, st));  // the blocks after the seeded ones, and all digests
+    if (h->d.rng_mode != CTF_RNG_COUNTER_DIRECT)
+        HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, st));  // the blocks after the seeded ones, and all digests
     HIP_TRY(hipStreamSynchronize(st));  // the host arrays are the caller's; do not outlive the call
     return CTF_OK;
 }
 
-static int need_mode(const ctf_env* h, int mode, const char* what) {
-    if (h->d.rng_mode != mode)
-        return fail(CTF_E_INVALID, "%s: the handle runs in %s mode", what, h->d.rng_mode == CTF_RNG_COUNTER ? "counter-RNG" : "MT19937");
+// `modes`: bit m set = the entry point serves rng_mode m
+static int need_mode(const ctf_env* h, unsigned modes, const char* what) {
+    static const char* const names[3] = {"MT19937", "counter-RNG", "counter-direct-RNG"};
+    if (!((modes >> h->d.rng_mode) & 1u)) return fail(CTF_E_INVALID, "%s: the handle runs in %s mode", what, names[h->d.rng_mode]);
     return CTF_OK;
 }
+#define MODE_MT (1u << CTF_RNG_MT19937)
+#define MODE_COUNTERS ((1u << CTF_RNG_COUNTER) | (1u << CTF_RNG_COUNTER_DIRECT))
 
 extern "C" int ctf_set_rng_state(ctf_env* h, int32_t e, const uint32_t* py, const uint32_t* np_) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
-    if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_set_rng_state")) return rc;
+    if (int rc = need_mode(h, MODE_MT, "ctf_set_rng_state")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(hipDeviceSynchronize());
     const uint32_t* src[2] = {py, np_};
@@ -281,7 +287,7 @@ extern "C" int ctf_set_rng_state(ctf_env* h, int32_t e, const uint32_t* py, cons
 extern "C" int ctf_get_rng_state(ctf_env* h, int32_t e, uint32_t* py, uint32_t* np_) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (e < 0 || e >= h->d.n_envs) return fail(CTF_E_RANGE, "env index %d", e);
-    if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_get_rng_state")) return rc;
+    if (int rc = need_mode(h, MODE_MT, "ctf_get_rng_state")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(hipDeviceSynchronize());
     uint32_t* dst[2] = {py, np_};
@@ -297,7 +303,7 @@ extern "C" int ctf_get_rng_state(ctf_env* h, int32_t e, uint32_t* py, uint32_t* 
 extern "C" int ctf_set_rng_states(ctf_env* h, const uint32_t* py_dev, const uint32_t* np_dev, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!py_dev && !np_dev) return CTF_OK;
-    if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_set_rng_states")) return rc;
+    if (int rc = need_mode(h, MODE_MT, "ctf_set_rng_states")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_import_rng(h->d, h->p, py_dev, np_dev, 0, h->d.n_envs, (hipStream_t)stream));
     HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, (hipStream_t)stream));
@@ -307,7 +313,7 @@ extern "C" int ctf_set_rng_states(ctf_env* h, const uint32_t* py_dev, const uint
 extern "C" int ctf_get_rng_states(ctf_env* h, uint32_t* py_dev, uint32_t* np_dev, void* stream) {
     if (!h) return fail(CTF_E_INVALID, "null handle");
     if (!py_dev && !np_dev) return CTF_OK;
-    if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_get_rng_states")) return rc;
+    if (int rc = need_mode(h, MODE_MT, "ctf_get_rng_states")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_export_rng(h->d, h->p, py_dev, np_dev, 0, h->d.n_envs, (hipStream_t)stream));
     return CTF_OK;
@@ -315,7 +321,7 @@ extern "C" int ctf_get_rng_states(ctf_env* h, uint32_t* py_dev, uint32_t* np_dev
 
 extern "C" int ctf_get_rng_counters(ctf_env* h, uint64_t* counters_dev, void* stream) {
     if (!h || !counters_dev) return fail(CTF_E_INVALID, "null argument");
-    if (int rc = need_mode(h, CTF_RNG_COUNTER, "ctf_get_rng_counters")) return rc;
+    if (int rc = need_mode(h, MODE_COUNTERS, "ctf_get_rng_counters")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_get_counters(h->d, h->p, (unsigned long long*)counters_dev, (hipStream_t)stream));
     return CTF_OK;
@@ -323,10 +329,10 @@ extern "C" int ctf_get_rng_counters(ctf_env* h, uint64_t* counters_dev, void* st
 
 extern "C" int ctf_set_rng_counters(ctf_env* h, const uint64_t* counters_dev, void* stream) {
     if (!h || !counters_dev) return fail(CTF_E_INVALID, "null argument");
-    if (int rc = need_mode(h, CTF_RNG_COUNTER, "ctf_set_rng_counters")) return rc;
+    if (int rc = need_mode(h, MODE_COUNTERS, "ctf_set_rng_counters")) return rc;
     DeviceScope guard(h->device);
     HIP_TRY(ctf_launch_set_counters(h->d, h->p, (const unsigned long long*)counters_dev, (hipStream_t)stream));
-    HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, (hipStream_t)stream));
+    if (h->d.rng_mode == CTF_RNG_COUNTER) HIP_TRY(ctf_launch_rng_refill(h->d, h->p, 0, h->d.n_envs, 1, (hipStream_t)stream));
     return CTF_OK;
 }
 
@@ -566,7 +572,7 @@ extern "C" int ctf_host_step(ctf_env* h, const int8_t* actions, const uint32_t* 
     if (h->d.n_envs != 1) return fail(CTF_E_INVALID, "ctf_host_step serves a handle of ONE env (this one has %d): batches use ctf_step / ctf_observe", h->d.n_envs);
     const bool rng_io = py_in || np_in || py_out || np_out;
     if (rng_io)
-        if (int rc = need_mode(h, CTF_RNG_MT19937, "ctf_host_step with generator states")) return rc;
+        if (int rc = need_mode(h, MODE_MT, "ctf_host_step with generator states")) return rc;
     for (const uint32_t* s : {py_in, np_in})
         if (s && s[CTF_MT_N] > CTF_MT_N) return fail(CTF_E_INVALID, "MT position %u > 624", s[CTF_MT_N]);
     DeviceScope guard(h->device);

@@ -87,7 +87,7 @@ static int derive(const ctf_config* c, int32_t n_envs, DevCfg* d) {
     if (C < 2 || C > 15) return fail(CTF_E_INVALID, "n_channels %d outside 2..15", C);
     if (c->game_steps < 1) return fail(CTF_E_INVALID, "game_steps must be >= 1");
     if (c->flip_axis < -1 || c->flip_axis > 2) return fail(CTF_E_INVALID, "flip_axis %d", c->flip_axis);
-    if (c->rng_mode != CTF_RNG_MT19937 && c->rng_mode != CTF_RNG_COUNTER) return fail(CTF_E_INVALID, "rng_mode %d", c->rng_mode);
+    if (c->rng_mode != CTF_RNG_MT19937 && c->rng_mode != CTF_RNG_COUNTER && c->rng_mode != CTF_RNG_COUNTER_DIRECT) return fail(CTF_E_INVALID, "rng_mode %d", c->rng_mode);
     for (int t = 0; t < 2; t++) {
         if (c->n_opponents[t] < 0 || c->n_opponents[t] > N) return fail(CTF_E_INVALID, "n_opponents[%d]", t);
         for (int k = 0; k < c->n_opponents[t]; k++)

@@ -16,6 +16,8 @@
 //   rngready u8 [E][2]        per stream: 1 = the other ring is in place; 2 + r = ring r is stale and waits for its regeneration
 //   rngage u8 [E][2]          per stream: step launches a stale ring has waited so far (k_step's tail blocks: theirs alone)
 //   rngctr u64 [E][6]         counter mode only (cfg.rng_mode == 1): stream index of word 0 of ring 0 / ring 1 (py), of ring 0 / 1 (np), seeds (py, np)
+//          u64 [E][4]         CTF_RNG_COUNTER_DIRECT (cfg.rng_mode == 2): words consumed (py, np), seeds (py, np) — the mode's whole RNG
+//                             state: the seven arrays above are 1-element placeholders that no kernel of the mode touches
 //   metric i32 [E][13][N]     agent-level counters (only when log_metrics)
 //   vislog u16 [512][E][N]    visitation LOG: entry (step % 512) = the cell of every agent after that step; the
 //                             maps are rebuilt from it on export, so a step writes 2N coalesced bytes per env
@@ -64,7 +66,7 @@ struct DevCfg {
     int32_t np_pairs;               // rand() draws of one step without respawns: sum over the agents that deal damage of their opponents
     uint32_t dmg_mask;              // bit i = AGENT_TYPE_DAMAGE[type(i)] > 0
     uint32_t flag_pack, capture_pack, spawn_pack;  // the two teams' cells: row 0 | col 0 << 8 | row 1 << 16 | col 1 << 24
-    int32_t rng_mode;               // CTF_RNG_MT19937 / CTF_RNG_COUNTER
+    int32_t rng_mode;               // CTF_RNG_MT19937 / CTF_RNG_COUNTER / CTF_RNG_COUNTER_DIRECT
     // the tile render (k_observe_tiles): envs are taken in groups of tile_k, the smallest count whose blocks fill a whole
     // number (tile_tpg) of tiles; div_ob_tile divides a tile's byte offset inside its group (a multiple of the tile size) by obs_bytes
     int32_t tile_k, tile_tpg;
@@ -97,7 +99,8 @@ struct DevPtrs {
     uint32_t* rngpos;
     uint8_t* rngready;
     uint8_t* rngage;
-    unsigned long long* rngctr;  // counter mode: u64 [E][6] = stream index of word 0 of each ring (py 0, py 1, np 0, np 1), stream seeds (py, np)
+    unsigned long long* rngctr;  // counter mode: u64 [E][6] = stream index of word 0 of each ring (py 0, py 1, np 0, np 1), stream seeds (py, np);
+                                 // CTF_RNG_COUNTER_DIRECT: u64 [E][4] = words consumed (py, np), stream seeds (py, np)
     uint32_t* py_top;
     uint32_t* np_hit;
     uint32_t* np_nib;

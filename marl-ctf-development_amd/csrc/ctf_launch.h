@@ -34,6 +34,8 @@ extern "C" {
 hipError_t ctf_launch_reset(const DevCfg&, const DevPtrs&, const uint8_t* mask, int init_perm, hipStream_t);
 hipError_t ctf_launch_step(const DevCfg&, const DevPtrs&, const StepArgs&, int with_tail, hipStream_t);
 hipError_t ctf_launch_step_observe(const DevCfg&, const DevPtrs&, const StepArgs&, const RenderArgs&, hipStream_t);
+// ---- ctf_step_direct.hip: the step of CTF_RNG_COUNTER_DIRECT, in the shape ctf_launch_step worked out (w lanes per env)
+hipError_t ctf_launch_step_direct(const DevCfg&, const DevPtrs&, const StepArgs&, int w, int n_step_blocks, size_t lds, hipStream_t);
 hipError_t ctf_launch_observe(const DevCfg&, const DevPtrs&, const RenderArgs&, int n_cus, hipStream_t);
 hipError_t ctf_launch_observe_codes(const DevCfg&, const DevPtrs&, uint8_t* codes, uint16_t* meta, uint16_t* selfcells, uint32_t reverse_mask,
                                     int n_cus, hipStream_t);

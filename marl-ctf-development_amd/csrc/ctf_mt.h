@@ -25,6 +25,7 @@
 //
 // Counter mode (CTF_RNG_COUNTER): the same rings and digests, but block k of a stream is words [624 k, 624 k + 624) of
 // Philox4x32-10(key = the stream's seed, counter = (word / 4, stream, "CTF1")) and the words are used as they are (no tempering).
+// CTF_RNG_COUNTER_DIRECT reads the same tape with ctr_block() inside the step and keeps no rings (ctf_step_core.h).
 #pragma once
 #include <stdint.h>
 

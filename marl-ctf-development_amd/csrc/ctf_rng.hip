@@ -4,7 +4,7 @@
 //   k_seed                           twin MT19937 seeding per env (CPython init_by_array / NumPy init_genrand), or the counter streams
 //   k_rng_refill                     every stale ring of a range of envs, one wave per ring
 //   k_import_rng / k_export_rng      the generators in their standard form (624 words + position)
-//   k_get_counters / k_set_counters  counter mode: words consumed per stream
+//   k_get_counters / k_set_counters  the two counter modes: words consumed per stream
 #include <hip/hip_runtime.h>
 
 #include "ctf_launch.h"
@@ -50,6 +50,11 @@ extern "C" __global__ void k_seed(DevCfg cfg, DevPtrs p, const uint64_t* py_seed
     uint32_t* a_py = p.mt_py + (size_t)e * 2 * CTF_MT_N;
     uint32_t* a_np = p.mt_np + (size_t)e * 2 * CTF_MT_N;
     const uint64_t ps = py_seeds[e], ns = np_seeds[e];
+    if (cfg.rng_mode == CTF_RNG_COUNTER_DIRECT) {  // both tapes at word 0: that is all there is (the rings are placeholders)
+        unsigned long long* ctr = p.rngctr + 4 * (size_t)e;
+        ctr[0] = 0; ctr[1] = 0; ctr[2] = ps; ctr[3] = ns;
+        return;
+    }
     if (cfg.rng_mode == CTF_RNG_COUNTER) {
         for (unsigned long long blk = 0; blk < CTF_MT_N / 4; blk++) {
             ctr_block(ps, blk, 0u, a_py + 4 * blk);
@@ -130,6 +135,11 @@ extern "C" __global__ void __launch_bounds__(256) k_export_rng(DevCfg cfg, DevPt
 extern "C" __global__ void k_get_counters(DevCfg cfg, DevPtrs p, unsigned long long* out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= cfg.n_envs) return;
+    if (cfg.rng_mode == CTF_RNG_COUNTER_DIRECT) {
+        out[2 * (size_t)e] = p.rngctr[4 * (size_t)e];
+        out[2 * (size_t)e + 1] = p.rngctr[4 * (size_t)e + 1];
+        return;
+    }
     for (int k = 0; k < 2; k++) {
         const uint32_t rp = p.rngpos[2 * e + k];
         out[2 * (size_t)e + k] = p.rngctr[6 * (size_t)e + 2 * k + CTF_RP_CUR(rp)] + CTF_RP_POS(rp);
@@ -139,6 +149,11 @@ extern "C" __global__ void k_get_counters(DevCfg cfg, DevPtrs p, unsigned long l
 extern "C" __global__ void k_set_counters(DevCfg cfg, DevPtrs p, const unsigned long long* in) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= cfg.n_envs) return;
+    if (cfg.rng_mode == CTF_RNG_COUNTER_DIRECT) {
+        p.rngctr[4 * (size_t)e] = in[2 * (size_t)e];
+        p.rngctr[4 * (size_t)e + 1] = in[2 * (size_t)e + 1];
+        return;
+    }
     unsigned long long* ctr = p.rngctr + 6 * (size_t)e;
     for (int k = 0; k < 2; k++) {
         const unsigned long long n = in[2 * (size_t)e + k], blk = n / CTF_MT_N;

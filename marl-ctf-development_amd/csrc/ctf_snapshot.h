@@ -8,6 +8,7 @@
 //   py_top   u32 [2][176]   np_hit u32 [2][26]   np_nib u32 [2][92]   (digests and mirrors)
 //   rng      16 B   u32 rngpos[2] | u8 rngready[2], u8 rngage[2] | zeros
 //   rngctr   u64 [6]                                  (counter mode only)
+// (CTF_RNG_COUNTER_DIRECT: the five ring / digest segments and the rng segment are absent; rngctr u64 [4] is the RNG segment)
 //   metrics  i32 [13][N], padded to 16 B              (log_metrics only)
 //   vis      u32 [N][GS]                              (log_metrics only)
 //   vislog   u16 [512][N], slot order                 (log_metrics only)
@@ -75,13 +76,17 @@ static inline SnapLayout snap_layout(const DevCfg& d, const DevPtrs& p, uint64_t
     };
     add(p.rec, d.RS, CTF_SNAP_VEC);
     add(p.grid, d.GS, CTF_SNAP_VEC);
-    add(p.mt_py, 2 * CTF_MT_N * 4, CTF_SNAP_VEC);
-    add(p.mt_np, 2 * CTF_MT_N * 4, CTF_SNAP_VEC);
-    add(p.py_top, 2 * CTF_P8_DW * 4, CTF_SNAP_VEC);
-    add(p.np_hit, 2 * CTF_HB_DW * 4, CTF_SNAP_VEC);
-    add(p.np_nib, 2 * CTF_NB_DW * 4, CTF_SNAP_VEC);
-    add(nullptr, 16, CTF_SNAP_RNG);
-    if (d.rng_mode == CTF_RNG_COUNTER) add(p.rngctr, 6 * 8, CTF_SNAP_VEC);
+    if (d.rng_mode == CTF_RNG_COUNTER_DIRECT) {
+        add(p.rngctr, 4 * 8, CTF_SNAP_VEC);
+    } else {
+        add(p.mt_py, 2 * CTF_MT_N * 4, CTF_SNAP_VEC);
+        add(p.mt_np, 2 * CTF_MT_N * 4, CTF_SNAP_VEC);
+        add(p.py_top, 2 * CTF_P8_DW * 4, CTF_SNAP_VEC);
+        add(p.np_hit, 2 * CTF_HB_DW * 4, CTF_SNAP_VEC);
+        add(p.np_nib, 2 * CTF_NB_DW * 4, CTF_SNAP_VEC);
+        add(nullptr, 16, CTF_SNAP_RNG);
+        if (d.rng_mode == CTF_RNG_COUNTER) add(p.rngctr, 6 * 8, CTF_SNAP_VEC);
+    }
     if (d.log_metrics) {
         const int32_t mb = CTF_N_METRICS * d.N * 4;
         add(p.metrics, mb, mb % 16 == 0 ? CTF_SNAP_VEC : CTF_SNAP_WORDS);

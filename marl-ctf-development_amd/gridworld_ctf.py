@@ -78,13 +78,14 @@ class VecGridworldCtf:
         virtual address range after a free / re-allocate: it is the physical backing, profiles/r02_alloc_probe*.txt)."""
         torch = _torch()
         self._lib = _lib or _abi.load_library()  # _lib: a side-by-side build, profiling only (tools/ab_inproc.py)
-        if rng_mode not in ("mt19937", "counter"):
-            raise ValueError("rng_mode must be 'mt19937' (the reference's generators, bit for bit) or 'counter'")
+        modes = {"mt19937": _abi.RNG_MT19937, "counter": _abi.RNG_COUNTER, "counter_direct": _abi.RNG_COUNTER_DIRECT}
+        if rng_mode not in modes:
+            raise ValueError("rng_mode must be 'mt19937' (the reference's generators, bit for bit), 'counter' or 'counter_direct'")
         # "counter": opt-in counter-based streams (include/ctf_env.h CTF_RNG_COUNTER) — word n of an env's stream is
-        # Philox4x32-10(seed, n); the draws are made from those words by the reference's own rules
+        # Philox4x32-10(seed, n); the draws are made from those words by the reference's own rules.  "counter_direct": the same
+        # streams, so the same trajectories, with no generator words stored (CTF_RNG_COUNTER_DIRECT: 32 bytes of RNG state per env)
         self.rng_mode = rng_mode
-        self.cfg, self.derived = _config.build_config(env_kwargs, log_metrics=log_metrics,
-                                                      rng_mode=_abi.RNG_COUNTER if rng_mode == "counter" else _abi.RNG_MT19937)
+        self.cfg, self.derived = _config.build_config(env_kwargs, log_metrics=log_metrics, rng_mode=modes[rng_mode])
         if not torch.cuda.is_available():
             raise _abi.CtfLibraryError("no HIP device visible: the GridworldCtf kernels need a GPU (there is no CPU fallback)")
         if device is None:
@@ -300,14 +301,14 @@ class VecGridworldCtf:
         return a, b
 
     def get_rng_counters(self):
-        """counter mode: int64 CUDA tensor [E, 2] = words consumed so far from the `random` / np.random stream of every env (the
+        """counter / counter_direct mode: int64 CUDA tensor [E, 2] = words consumed so far from the `random` / np.random stream of every env (the
         whole RNG state of an env there, besides its two seeds).  Stream-ordered."""
         out = _torch().empty((self.n_envs, 2), dtype=_torch().int64, device=self.device)
         self._call("ctf_get_rng_counters", _abi.ptr(out), self._stream())
         return out
 
     def set_rng_counters(self, counters):
-        """counter mode: the way back (int64 CUDA tensor [E, 2]) — a checkpoint restore after ``seed``."""
+        """counter / counter_direct mode: the way back (int64 CUDA tensor [E, 2]) — a checkpoint restore after ``seed``."""
         self._call("ctf_set_rng_counters", self._check_dev(counters, _torch().int64, self.n_envs * 2), self._stream())
 
     # -- the hot path -------------------------------------------------------------------------
