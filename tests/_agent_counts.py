@@ -22,6 +22,7 @@ CONFIGS = [(n, lop) for n in range(2, 17) for lop in (0, 1) if not (lop and n ==
 LANE_CONFIGS = [(10, 1), (12, 1), (14, 1), (16, 1), (9, 0), (13, 0), (15, 0)]
 COUNTER_N = (3, 6, 12, 15, 16)  # the snapshot also in counter mode
 BARE_N = (5, 16)                # ... and with log_metrics off
+DIRECT_STEPS, DIRECT_DROP_CAP = 40, 2  # the counter_direct run: one episode and ten steps; the envs a config may lose to a full spawn window
 
 
 def config_id(c):

@@ -206,7 +206,10 @@ def _in_window(map_name, s, i):
 
 
 def _np_words(a, b):
-    """words the np.random generator gave out between two states of one step (fewer than 624)"""
+    """words the np.random generator gave out between two states of one step (fewer than 624): from the MT position keys, or, on a
+    counter tape, from the words consumed"""
+    if "np_words" in a:
+        return int(b["np_words"]) - int(a["np_words"])
     return (int(b["np_pos"]) - int(a["np_pos"])) % 624
 
 
@@ -454,6 +457,7 @@ def snapshot(env, counter=False):
     del s["visitation"]
     if counter:
         s["rng"] = np.array(env.get_rng_counters(), np.int64)
+        s.update(py_words=int(s["rng"][0]), np_words=int(s["rng"][1]))  # (what the MT position keys are to the predicates)
     else:
         py, npw = env.get_rng_state()
         s.update(py=py, np=npw, py_pos=int(py[624]), np_pos=int(npw[624]))
@@ -483,11 +487,16 @@ def oracle_step(env, sc, t, counter=False, auto_reset=None):
     return out
 
 
-def run_oracle(sc, r, cfg=None):
-    """-> (state before, [outputs of every step])"""
-    env = oracle_env(sc, r, cfg)
-    before = snapshot(env)
-    return before, [oracle_step(env, sc, t) for t in range(len(sc.actions))]
+def counter_seeds(sc, r):
+    """the two seeds of replica r on the counter tape (counter mode takes any two 64-bit values)"""
+    return seed_of(sc, r), seed_of(sc, r) ^ 0x5DEECE66D
+
+
+def run_oracle(sc, r, cfg=None, counter=False):
+    """-> (state before, [outputs of every step]); ``counter``: on the counter tape (``cfg`` then is a counter-mode config)"""
+    env = oracle_env(sc, r, cfg, seeds=counter_seeds(sc, r) if counter else None)
+    before = snapshot(env, counter)
+    return before, [oracle_step(env, sc, t, counter=counter) for t in range(len(sc.actions))]
 
 
 def event(sc, before, outs):

@@ -34,6 +34,7 @@ def runs():
         out[n, lop, "stagger"] = ac.oracle_run(cfg, ac.seeds(), ac.STEPS, stagger=True)
         if n in ac.COUNTER_N:
             out[n, lop, "counter"] = ac.oracle_run(ac.build(n, lop, counter=True), ac.seeds(), ac.STEPS)
+        out[n, lop, "direct"] = ac.oracle_run(ac.build(n, lop, counter=True), ac.seeds(), ac.DIRECT_STEPS)
         if (n, lop) in ac.LANE_CONFIGS:
             out[n, lop, "lanes"] = ac.oracle_run(cfg, ac.lane_seeds(), ac.LANE_STEPS, act_seed=ac.LANE_SEED, env_offset=ac.LANE_OFFSET)
     return out
@@ -67,6 +68,29 @@ def test_every_run_keeps_its_envs_and_ends_episodes(runs, config):
         assert (r["episodes"][r["alive"]] >= 1).all(), f"{which}: a surviving env ends no episode"
     ac.lockstep_mask(runs[n, lop, "main"]["alive_at_30"])  # (asserts that 7 and 9 survivors can be picked)
     assert runs[n, lop, "main"]["alive_at_30"][64:].any()
+
+
+@pytest.mark.parametrize("config", ac.CONFIGS, ids=IDS)
+def test_the_counter_direct_run_keeps_its_envs_and_ends_an_episode(runs, config):
+    """test_counter_direct_step_at_every_count's input, at its seeds, action stream and steps, on the counter tape"""
+    r = runs[config[0], config[1], "direct"]
+    assert len(r["alive"]) == ac.E and int((~r["alive"]).sum()) <= ac.DIRECT_DROP_CAP, f"the oracle drops {(~r['alive']).sum()} envs"
+    assert (r["episodes"][r["alive"]] == 1).all(), "every followed env ends one episode"
+
+
+def test_the_larger_counts_draw_past_the_np_window():
+    """a step's tag compares take two np.random words per (damage-dealing agent, opponent) pair: more than the window's bytes from
+    9-even and 12-lop upwards, where the last compares of every step are computed on demand"""
+    import _counter_direct_cases as cd
+
+    np_cap = cd.window_caps()[0]
+    words = {}
+    for n, lop in ac.CONFIGS:
+        cfg = ac.build(n, lop, counter=True)
+        assert all(cfg.type_damage[cfg.agent_type[i]] > 0 for i in range(n))
+        words[n, lop] = 2 * sum(int(cfg.n_opponents[cfg.agent_team[i]]) for i in range(n))
+    past = sorted(c for c, w in words.items() if w > np_cap)
+    assert past == sorted([(n, 0) for n in range(9, 17)] + [(n, 1) for n in range(12, 17)]), words
 
 
 def test_the_sweep_sees_captures_and_the_last_counter_word(runs):

@@ -1,17 +1,22 @@
 """rng_mode="counter_direct" (include/ctf_env.h CTF_RNG_COUNTER_DIRECT) without a GPU: the step core compiled for the host in that
 mode and stepped against the oracle in counter mode as a stand-alone program under AddressSanitizer + UBSan
 (tests/hostsim/direct_main.cpp), in the shipped window sizes and with the windows shrunk to a few words; the boundary (header,
-binding, constructor); and, on the oracle alone, the conditions the GPU tests' inputs have to meet."""
+binding, constructor); and, on the oracle alone, the conditions the GPU tests' inputs have to meet: the beyond-the-window batch, the
+tie cases (tests/_tie_cases.py) and the ends of the threshold of tests/test_gpu_direct_edges.py, and the planted rule table on the
+counter tape (tests/test_gpu_rules.py)."""
 import ctypes
 import importlib
 import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 import _counter_direct_cases as cd
 import _rule_cases as rc
+import _tie_cases as tc
+import oracle
 from _cases import Case, abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,7 +57,11 @@ def test_the_direct_step_on_the_host_under_sanitizers_matches_the_oracle(build, 
     subprocess.check_call([_llvm("clang"), "-std=c11", "-Wall", "-Wno-unknown-pragmas", *san, "-c", "-o", obj, os.path.join(ROOT, "oracle", "ctf_oracle.c")])
     subprocess.check_call([_llvm("clang++"), "-std=c++17", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "marl-ctf-development_amd", "csrc"),
                            *san, *BUILDS[build], "-o", exe, os.path.join(sim, "direct_main.cpp"), obj, "-lm"])
-    out = subprocess.run([exe, *_config_files(tmp_path)], capture_output=True, text=True, timeout=600)
+    tie_cfg = tc.config(0.5)  # (the sweep sets TAG_PROBABILITY itself)
+    tie_path = str(tmp_path / "tie16.cfg")
+    with open(tie_path, "wb") as f:
+        f.write(ctypes.string_at(ctypes.addressof(tie_cfg), ctypes.sizeof(tie_cfg)))
+    out = subprocess.run([exe, *_config_files(tmp_path), "--ties", tie_path], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-3000:] + "\n" + out.stderr[-3000:]
     assert "all direct-mode cases passed" in out.stdout
     rows = {m.group(1): m for m in re.finditer(r"OK \S*?(\w+)\.cfg: N (\d+), (\d+) env-steps, .*? py (\d+) np (\d+), tags (\d+) respawns (\d+)", out.stdout)}
@@ -67,7 +76,22 @@ def test_the_direct_step_on_the_host_under_sanitizers_matches_the_oracle(build, 
             assert py_beyond == steps and np_beyond == steps, out.stdout
     if build == "shipped":     # ... and 16 agents leave the shipped ones
         assert int(rows["tag16"].group(5)) == int(rows["tag16"].group(3)), out.stdout
-
+    # the tie sweep: per residue of n* the deciding k and where their draws lie in the window of THIS build, as the program counted
+    # them while it compared every (r, k, variant) with the oracle — and as the oracle alone gives them here
+    ties = {(int(m.group(1)), int(m.group(2))): tuple(int(x) for x in m.groups()[2:])
+            for m in re.finditer(r"TIES \S+: py (\d+), r (\d), deciding (\d+) of (\d+) k, b \+ 1 < fill (\d+), b == fill - 1 (\d+), b >= fill (\d+)", out.stdout)}
+    assert sorted(ties) == [(pc, r) for pc in (tc.PY_COUNTER, tc.EARLY_PY_COUNTER) for r in tc.RESIDUES], out.stdout
+    fill = cd.window_caps()[0] if build == "shipped" else 8
+    for (pc, r), (deciding, pairs, inside, edge, beyond) in ties.items():
+        assert pairs == tc.PAIRS and deciding >= 40 and inside + edge + beyond == deciding, out.stdout
+        classes = [tc.position_class(tc.window_byte(r, k), fill) for k in tc.deciding(r, pc)]
+        assert (deciding, inside, edge, beyond) == (len(classes), classes.count("inside"), classes.count("edge"), classes.count("beyond")), out.stdout
+        # every class where it can occur: b = n* mod 4 and fill - 1 = 3 mod 4; the GPU tests' shuffle (PY_COUNTER) has its first
+        # deciding draw at b >= 10, inside the shipped window and past the shrunk one, the early shuffle at b <= 3
+        if build == "shipped" or pc == tc.EARLY_PY_COUNTER:
+            assert inside > 0 and beyond > 0 and (edge > 0) == (r == 3), out.stdout
+        else:
+            assert beyond == deciding, out.stdout
 
 def test_header_binding_and_constructor_know_the_mode():
     text = open(os.path.join(ROOT, "include", "ctf_env.h")).read()
@@ -103,3 +127,90 @@ def test_the_beyond_the_window_batch_meets_its_condition_on_the_oracle():
     assert all(row[2] == 0 for rows in runs for row in rows), "no env of the batch may leave the rules (status)"
     respawns = sum(int(rows[-1][3]["metrics"][rc.M["respawn_tag_count"]].sum()) for rows in runs)
     assert respawns >= 4 * len(runs), respawns
+
+
+# ---- the tie cases ------------------------------------------------------------------------------------------------------------------------
+def test_the_tie_thresholds_are_what_the_step_core_derives():
+    """ceil(p * 2**53) of the three variants is X, X + 1 and the next multiple of 2**26, and the tape words are ctr_block's (the
+    oracle in counter mode consumes the words the generator here computes: a step that hits at X + 1 and misses at X says so)"""
+    for r in tc.RESIDUES:
+        x = tc.draw_integer(tc.N_STAR + r)
+        thr = [int(tc.probability(r, v) * 2.0 ** 53) for v in tc.VARIANTS]
+        assert thr == [x, x + 1, ((x >> 26) + 1) << 26] and 0 < x and thr[2] <= 2 ** 53
+        assert thr[2] > thr[1], "the next-hi variant needs a draw whose low 26 bits are not all ones"
+    text = open(cd.CORE).read()
+    assert "for (uint32_t t = (uint32_t)j; t < nb + pb; t += W)" in text, "tc.parking_lane restates this loop: block t is lane t % W's"
+    assert re.search(r"#define\s+NP_DIRECT_SLACK\s+2\b", text)
+
+
+@pytest.mark.parametrize("r", tc.RESIDUES)
+def test_the_tie_cases_meet_their_conditions_on_the_oracle(r):
+    """what tests/test_gpu_direct_edges.py relies on: the step draws exactly 256 np.random words (no respawn), at least 40 of the 128
+    k are deciding, their draws lie at every position of the window the residue allows, and the three variants decide as named"""
+    np_cap = cd.window_caps()[0]
+    assert np_cap == 68 and 2 * tc.PAIRS + 2 >= np_cap  # the window is full: fill = NP_DIRECT_BYTES
+    rows, ks = tc.first_step(r), tc.deciding(r)
+    for v in tc.VARIANTS:
+        for k in range(tc.PAIRS):
+            hp, words, status, tags = rows[v][k]
+            assert status == 0 and words[0] > tc.PY_COUNTER and words[1] == tc.np_counter(r, k) + 2 * tc.PAIRS, (v, k, words)
+    assert len(ks) >= 40, len(ks)
+    for k in range(tc.PAIRS):
+        tie, plus, nxt = (rows[v][k][0] for v in tc.VARIANTS)
+        assert np.array_equal(plus, nxt), k
+        if k in ks:  # the draw at n* is the one difference: one agent is hit once more (less the heal's clamp at full hp)
+            assert (tie != plus).sum() == 1 and (tie >= plus).all(), k
+            assert rows["tie+1"][k][3] == rows["next-hi"][k][3] == rows["tie"][k][3] + 1
+    bs = [tc.window_byte(r, k) for k in ks]
+    assert all(b % 4 == r for b in bs)
+    assert any(b < np_cap - 2 for b in bs) and any(b >= np_cap for b in bs)
+    assert ((np_cap - 2) in bs) == (r == 2), "the last pair wholly inside the window"
+    assert ((np_cap - 1) in bs) == (r == 3), "first byte parked, second not"
+    classes = {tc.position_class(b, np_cap) for b in bs}
+    assert classes == ({"inside", "edge", "beyond"} if r == 3 else {"inside", "beyond"})
+    if r == 3:  # the straddle: the two bytes of every in-window draw sit in different dwords, parked by different lanes from W = 2 on
+        inside = [b for b in bs if b + 1 < np_cap]
+        assert inside and all(tc.parking_lane(b, w) != tc.parking_lane(b + 1, w) for b in inside for w in (2, 4, 8))
+    print(f"n* = {tc.N_STAR + r}: {len(ks)} deciding k; b < {np_cap - 2}: {sum(b < np_cap - 2 for b in bs)}, b = {np_cap - 2}: {bs.count(np_cap - 2)}, "
+          f"b = {np_cap - 1}: {bs.count(np_cap - 1)}, b >= {np_cap}: {sum(b >= np_cap for b in bs)}")
+
+
+def _ends_run(p):
+    """test_the_ends_of_the_threshold's run on the oracle alone -> per env (tag_count sum, the trajectory's bytes)"""
+    E, steps = 16, 6
+    py, npz = cd.seeds(E)
+    cfg = tc.config(p)
+    out = []
+    for e in range(E):
+        env = oracle.OracleEnv(cfg)
+        env.seed(int(py[e]), int(npz[e]))
+        trace = []
+        for t in range(steps):
+            o = tc.twin_step(env, oracle.philox_actions(tc.N_AGENTS, tc.FOLLOW_SEED, t, e))
+            # (the spawns lie in two corners: from step 4 on, at TAG_PROBABILITY 1, a respawn may land past row / column 0, which
+            # the step reports and both sides place alike; nothing else may be reported, and never "no respawn cell")
+            assert o["status"] & ~abi.ST_SPAWN_EDGE == 0 and (p > 0.5 or o["status"] == 0)
+            trace.append(b"".join(np.ascontiguousarray(o[k]).tobytes() for k in ("grid", "pos", "hp", "metrics", "r64", "rng")))
+        out.append((int(o["metrics"][rc.M["tag_count"]].sum()), b"".join(trace)))
+    return out
+
+
+def test_the_ends_of_the_threshold_on_the_oracle():
+    for p in (0.0, 2.0 ** -53):
+        assert all(tags == 0 for tags, _ in _ends_run(p)), p
+    one, nearly = _ends_run(1.0), _ends_run(1.0 - 2.0 ** -53)
+    assert one == nearly and all(tags > 0 for tags, _ in one)
+
+
+# ---- the planted rule table on the counter tape -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sc", rc.SCENARIOS, ids=[s.name for s in rc.SCENARIOS])
+def test_every_planted_event_takes_place_on_the_counter_tape(sc):
+    """tests/test_gpu_rules.py in counter_direct: seeded (s, s ^ 0x5DEECE66D), every scenario's predicate is evaluable on a counter
+    snapshot (words consumed stand in for the MT positions) and its event takes place in at least one of the 8 replicas"""
+    cfg = rc.build(sc.map, sc.consts, counter=True)[0]
+    runs = [rc.run_oracle(sc, r, cfg, counter=True) for r in range(rc.R)]
+    if sc.status_only:
+        assert all(outs[-1]["status"] == abi.ST_NO_RESPAWN for _, outs in runs)
+        return
+    assert all(o["status"] == 0 for _, outs in runs for o in outs)
+    assert sum(rc.event(sc, *run) for run in runs) >= 1

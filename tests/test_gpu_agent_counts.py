@@ -545,3 +545,36 @@ def test_states_export_and_import_at_every_count(config):
     _status_ok(x, followers)
     assert y.status() & ~abi.ST_NO_RESPAWN == 0
     x.close(), y.close()
+
+
+# ---- (f) the step in rng_mode="counter_direct" ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("config", ac.CONFIGS, ids=IDS)
+def test_counter_direct_step_at_every_count(config):
+    """The Philox tape drawn inside the step kernel, whose windows are sized from N and the number of tagging pairs and whose blocks
+    are spread over the env's lanes: 40 auto-reset steps against counter-mode oracles (the same tape, their own float64 compare at
+    TAG_PROBABILITY 0.75): every step f64 rewards, done and the words consumed from both tapes, every tenth step and at the end the
+    full state views.  From 9-even / 12-lop upwards a step draws more np.random words than the window holds: the compares past it
+    are computed where the draw stands."""
+    n = config[0]
+    seeds = ac.seeds()
+    vec = _make(config, seeds, rng_mode="counter_direct")
+    g = vec.GRID_SIZE
+    followers = _followers(ac.build(*config, counter=True), seeds)
+    for t in range(ac.DIRECT_STEPS):
+        a = np.stack([oracle.philox_actions(n, ac.ACT_SEED, t, e) for e in range(E)])
+        vec.step(torch.from_numpy(a).to(vec.device), auto_reset=True, want_f64=True)
+        r64, d, ctr = vec.rewards64.cpu().numpy(), vec.done.cpu().numpy(), vec.get_rng_counters().cpu().numpy()
+        full = t % 10 == 9 or t == ac.DIRECT_STEPS - 1
+        for e, f in enumerate(followers):
+            out = f.step(a[e])
+            if out is None:
+                continue
+            ctx = f"{ac.config_id(config)} env {e} step {t}"
+            assert np.array_equal(_bits(r64[e]), _bits(out[0])) and int(d[e]) == int(out[1]), ctx
+            assert tuple(int(x) for x in ctr[e]) == f.env.get_rng_counters(), ctx + ": words consumed"
+            if full:
+                _same_view(view_arrays(vec.get_state(e), n, g), f.arrays(), ctx)
+    dropped = int((~_alive(followers)).sum())
+    assert dropped <= ac.DIRECT_DROP_CAP, dropped
+    _status_ok(vec, followers)
+    vec.close()
