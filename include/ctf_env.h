@@ -287,7 +287,10 @@ int ctf_observe_codes(ctf_env* env, uint8_t* codes_dev, uint16_t* meta_dev, uint
  * k_step_observe: the step's blocks, its ring regeneration, then the render's tiles, each of which waits only for the step
  * blocks of its own (one or two) envs — the same results bit for bit, but 9 % slower at 65 536 arena envs, so not the
  * default (profiles/r06_one_launch_step_observe.md).  (Step and render fused per env group, one wave doing
- * both, was measured in round 2 — 25 % slower: profiles/r02_fused_step_observe_ablation.md.) */
+ * both, was measured in round 2 — 25 % slower: profiles/r02_fused_step_observe_ablation.md.)
+ * In the two-launch form the metadata rows are written by the step kernel, which holds every env's final record, and the render
+ * runs without them (the same bits; meta_dev with obs_dev == NULL is one launch); CTF_STEP_META=0, read at every call, leaves them
+ * to the render as before (profiles/r15_step_meta.md). */
 int ctf_step_observe(ctf_env* env, const int8_t* actions_dev, float* rewards_f32_dev,
                      double* rewards_f64_dev, uint8_t* done_dev, uint8_t* obs_dev, uint16_t* meta_dev,
                      uint32_t reverse_mask, uint32_t flags, void* stream);

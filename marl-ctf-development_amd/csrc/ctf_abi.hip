@@ -459,6 +459,12 @@ extern "C" int ctf_observe_codes(ctf_env* h, uint8_t* codes, uint16_t* meta, uin
     return CTF_OK;
 }
 
+// CTF_STEP_META=0: the two-launch ctf_step_observe leaves the metadata rows to its render (A/B runs, tests); read at every call
+static bool step_meta_enabled() {
+    const char* e = getenv("CTF_STEP_META");
+    return !e || atoi(e) != 0;
+}
+
 extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, double* rw64, uint8_t* done, uint8_t* obs,
                                 uint16_t* meta, uint32_t reverse_mask, uint32_t flags, void* stream) {
     if (!h || !actions) return fail(CTF_E_INVALID, "null argument");
@@ -475,12 +481,19 @@ extern "C" int ctf_step_observe(ctf_env* h, const int8_t* actions, float* rw32, 
         if (retained_here(h, obs)) HIP_TRY(ctf_launch_obs_key_clear(h->shadow, h->d.n_envs, (hipStream_t)stream));
         return CTF_OK;
     }
-    HIP_TRY(ctf_launch_step(h->d, h->p, StepArgs{actions, rw32, rw64, done, flags}, 1, (hipStream_t)stream));
+    // The metadata rows come from the step kernel, which holds every env's final record in LDS and makes the rows of a wave's envs
+    // at once (ctf_meta.h); the render then runs without them — k_observe_delta as the instantiation that has none of their code —
+    // and with obs == NULL there is no second launch at all.  CTF_STEP_META=0: the render makes them, as it always did.
+    uint16_t* step_rows = step_meta_enabled() ? meta : nullptr;
+    uint16_t* render_rows = step_rows ? nullptr : meta;
+    StepArgs sa{actions, rw32, rw64, done, flags};
+    sa.meta = step_rows;
+    HIP_TRY(ctf_launch_step(h->d, h->p, sa, 1, (hipStream_t)stream));
     if (retained_here(h, obs)) {
-        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, meta, reverse_mask), delta_hint(h), h->delta_bitmap, h->delta_flags, (hipStream_t)stream));
-    } else if (obs || meta) {
+        HIP_TRY(ctf_launch_observe_delta(h->d, h->p, h->shadow, render_args(h, obs, render_rows, reverse_mask), delta_hint(h), h->delta_bitmap, h->delta_flags, (hipStream_t)stream));
+    } else if (obs || render_rows) {
         h->d.obs_store_nt = store_hint(h);
-        HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, meta, reverse_mask), h->n_cus, (hipStream_t)stream));
+        HIP_TRY(ctf_launch_observe(h->d, h->p, render_args(h, obs, render_rows, reverse_mask), h->n_cus, (hipStream_t)stream));
     }
     return CTF_OK;
 }

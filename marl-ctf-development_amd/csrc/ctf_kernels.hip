@@ -35,33 +35,12 @@ __device__ unsigned long long g_step_trace[8192][40];
 #define CTF_STAMP(k) do { if (((STEP_TRACE_MASK >> (k)) & 1ull) && threadIdx.x == 0 && blockIdx.x < 8192) g_step_trace[blockIdx.x][(k)] = wall_clock64(); } while (0)
 #endif
 #include "ctf_ring_dev.h"  // (and through it ctf_step_core.h: both after CTF_STAMP)
+#include "ctf_meta.h"
 
 // ------------------------------------------------------------------------------------------------
 // small helpers (fdiv, cheb, the SGPR-pinned config lookups, MT19937: ctf_step_core.h / ctf_mt.h)
 // ------------------------------------------------------------------------------------------------
-// NumPy npy_double_to_half: direct round-to-nearest-even f64 -> binary16 bits
-__device__ __forceinline__ uint16_t f64_to_f16(double d) {
-    uint64_t b = (uint64_t)__double_as_longlong(d);
-    uint32_t sign = (uint32_t)((b >> 48) & 0x8000u);
-    int32_t be = (int32_t)((b >> 52) & 0x7FF);
-    uint64_t m = b & 0xFFFFFFFFFFFFFull;
-    if (be == 0x7FF) return (uint16_t)(sign | 0x7C00u | (m ? (0x200u | (uint32_t)(m >> 42)) : 0u));
-    if (be == 0) return (uint16_t)sign;
-    int32_t E = be - 1023;
-    if (E > 15) return (uint16_t)(sign | 0x7C00u);
-    if (E >= -14) {
-        uint32_t h = (uint32_t)((E + 15) << 10) | (uint32_t)(m >> 42);
-        uint64_t rem = m & ((1ull << 42) - 1), half = 1ull << 41;
-        if (rem > half || (rem == half && (h & 1u))) h++;
-        return (uint16_t)(sign | h);
-    }
-    if (E < -25) return (uint16_t)sign;
-    uint64_t full = m | (1ull << 52);
-    int shift = 28 - E;
-    uint64_t h = full >> shift, rem = full & ((1ull << shift) - 1), half = 1ull << (shift - 1);
-    if (rem > half || (rem == half && (h & 1u))) h++;
-    return (uint16_t)(sign | (uint32_t)h);
-}
+// (the metadata values and f64_to_f16: ctf_meta.h)
 
 // ------------------------------------------------------------------------------------------------
 // reset
@@ -168,10 +147,11 @@ __device__ __forceinline__ void tail_block(const DevCfg& cfg, const DevPtrs& p, 
 #endif
 }
 // 16 blocks (= waves) per CU fit by LDS: the register budget is held to the matching 4 waves per SIMD (128 VGPRs)
-template <bool METRICS, int W>
+// META: the step blocks also write their envs' metadata rows (StepArgs.meta; step_block)
+template <bool METRICS, int W, bool META>
 __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
 k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restrict__ rw32, double* __restrict__ rw64,
-       uint8_t* __restrict__ done_out, uint32_t flags, int n_step_blocks) {
+       uint8_t* __restrict__ done_out, uint32_t flags, int n_step_blocks, StepMeta sm) {
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x;
     const int sb = (int)blockIdx.x;  // this step block's index
@@ -187,7 +167,7 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
         g_step_trace[blockIdx.x][39] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
                                        ((unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
 #endif
-    step_block<METRICS, W, false>(cfg, p, actions, rw32, rw64, done_out, flags, sb, lane, lds, StepPub{});
+    step_block<METRICS, W, false, false, META>(cfg, p, actions, rw32, rw64, done_out, flags, sb, lane, lds, StepPub{}, sm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -391,18 +371,10 @@ __device__ __forceinline__ void obs_build_env(const DevCfg& cfg, const DevPtrs& 
         const int32_t* misc = (const int32_t*)(srec + cfg.off_misc);
         if (lane < 36) {
             double val = 0.0;
-            if (lane == 0) val = (double)misc[0] / (double)cfg.game_steps;
-            else if (lane < 3) val = (double)(misc[lane] + 1) / (double)(misc[3 - lane] + 1);  // viewer team lane-1
-            else if (lane >= 4 && lane < 4 + N) {
-                // the quirk at :1039-1041: hp of the agent whose INDEX is type(j), over max hp of type(j), as uint8
-                const int tv = cfg_type(cfg, lane - 4);
-                double q = 0.0;
-                if (tv < N) {
-                    const uint32_t* hq = (const uint32_t*)(srec + 8 * tv);
-                    q = __hiloint2double((int)hq[1], (int)hq[0]) / sel4(cfg.type_hp, tv);
-                }
-                val = (double)(uint8_t)(long long)q;
-            } else if (lane >= 20 && lane < 20 + N) val = (double)srec[cfg.off_flag + lane - 20];
+            if (lane == META_MV_STEP) val = meta_step_fraction(misc[0], cfg.game_steps);
+            else if (lane < META_MV_RATIO + 2) val = meta_capture_ratio(misc[lane], misc[3 - lane]);  // viewer team lane-1
+            else if (lane >= META_MV_HP && lane < META_MV_HP + N) val = (double)meta_hp_u8(cfg, srec, lane - META_MV_HP);
+            else if (lane >= META_MV_FLAG && lane < META_MV_FLAG + N) val = (double)srec[cfg.off_flag + lane - META_MV_FLAG];
             mv[lane] = f64_to_f16(val);
         }
         __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
@@ -730,7 +702,9 @@ __host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int CGG, i
 
 #define OBS_DELTA_IMG_REGS 2  // 16-byte units of the shadow's images a lane loads with the first loads (the arena needs one)
 
-template <int STORE_NT, bool REBUILD>
+// META = false: the caller has the rows from elsewhere (ctf_step_observe: k_step wrote them, ctf_meta.h) — no record load, no
+// record parking and no obs_build_env in the kernel at all; `meta` is then not looked at.
+template <int STORE_NT, bool REBUILD, bool META>
 __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
                                                        uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map, uint32_t all_dirty) {
     extern __shared__ uint32_t lds[];
@@ -755,7 +729,8 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     const uint32_t* gcur = (const uint32_t*)(p.grid + (size_t)e * cfg.GS);
     uint32_t* gsh = (uint32_t*)(sh.grid + (size_t)e * cfg.GS);
     const uint8_t* rec = p.rec + (size_t)e * cfg.RS;
-    const uint32_t recw = ((const uint32_t*)rec)[min(lane, cfg.RS / 4 - 1)];
+    uint32_t recw = 0u;
+    if constexpr (META) recw = ((const uint32_t*)rec)[min(lane, cfg.RS / 4 - 1)];
     const uint32_t cur_pos = *(const uint16_t*)(rec + cfg.off_pos + 2 * min(lane, N - 1));
     uint32_t cur[4], old[4];
 #pragma unroll
@@ -807,7 +782,8 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
         for (int q = lane + WAVE * OBS_DELTA_IMG_REGS; q < n_iu; q += WAVE)  // larger shapes: the rest, loaded here
             ((u32x4_t*)images)[image_unit(q)] = ((const u32x4_t*)ish)[image_unit(q)];
     }
-    if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
+    if constexpr (META)
+        if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
     if (lane < ndw) {
         const int left = nl - 32 * lane;
         lmask[lane] = (known && !all_dirty) ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
@@ -853,8 +829,9 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     }
 
     const ObsSlots no_slots = {{0, 0, 0, 0}};
-    if (OBS_DELTA_META_FIRST && meta)
-        obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
+    if constexpr (META && OBS_DELTA_META_FIRST)
+        if (meta)
+            obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
 
     // ---- 3. the dirty lines of the env's span: one changed cell per lane, then the viewers that moved
     if (known) {
@@ -944,8 +921,9 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     }
 
     // ---- 5. the metadata rows, whole (obs_build_env parks the record in LDS and makes them from it)
-    if (!OBS_DELTA_META_FIRST && meta)
-        obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
+    if constexpr (META && !OBS_DELTA_META_FIRST)
+        if (meta)
+            obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
 
     // ---- 6. the shadow follows what the buffer now holds
 #pragma unroll
@@ -1460,8 +1438,10 @@ extern "C" hipError_t ctf_launch_step(const DevCfg& cfg, const DevPtrs& p, const
     }
     const StepShape s = step_shape(cfg, w, cfg.log_metrics != 0, with_tail && cfg.rng_refill_every, true);
     with_step_variant(cfg.log_metrics != 0, w, [&](auto M, auto W) {
-        hipLaunchKernelGGL((k_step<M.value, W.value>), dim3(s.nstep + s.ntail), dim3(WAVE), s.lds, st, cfg, p, a.actions, a.rw32, a.rw64, a.done,
-                           a.flags, s.nstep);
+        with_bool(a.meta != nullptr, [&](auto META) {
+            hipLaunchKernelGGL((k_step<M.value, W.value, META.value>), dim3(s.nstep + s.ntail), dim3(WAVE), s.lds, st, cfg, p, a.actions, a.rw32,
+                               a.rw64, a.done, a.flags, s.nstep, step_meta(cfg, a));
+        });
     });
     return hipGetLastError();
 }
@@ -1474,7 +1454,7 @@ extern "C" int ctf_debug_step_occupancy(int lds, int* blocks_per_cu, int* lds_pe
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 1;
     *lds_per_cu = (int)prop.maxSharedMemoryPerMultiProcessor;
     *lds_per_block = (int)prop.sharedMemPerBlock;
-    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_step<true, 4>, WAVE, (size_t)lds);
+    return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_step<true, 4, false>, WAVE, (size_t)lds);
 }
 #endif
 static int observe_align(const DevCfg& cfg, const uint8_t* obs) {
@@ -1567,8 +1547,10 @@ extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs&
                                r.reverse_mask, xcd_map);
         else
             with_bool((flags & CTF_OBS_DELTA_F_REBUILD) != 0u, [&](auto RB) {
-                hipLaunchKernelGGL((k_observe_delta<NT.value, RB.value>), dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta,
-                                   r.reverse_mask, xcd_map, (flags & CTF_OBS_DELTA_F_ALL_DIRTY) ? 1u : 0u);
+                with_bool(r.meta != nullptr, [&](auto META) {  // no rows asked for: the instantiation without any of their code
+                    hipLaunchKernelGGL((k_observe_delta<NT.value, RB.value, META.value>), dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs,
+                                       r.meta, r.reverse_mask, xcd_map, (flags & CTF_OBS_DELTA_F_ALL_DIRTY) ? 1u : 0u);
+                });
             });
     });
     return hipGetLastError();

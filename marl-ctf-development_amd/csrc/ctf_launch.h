@@ -18,6 +18,7 @@ struct StepArgs {
     double* rw64;
     uint8_t* done;
     uint32_t flags;
+    uint16_t* meta = nullptr;  // not NULL: the step also writes the envs' metadata rows f16 [E][N][M] (ctf_step_observe; ctf_meta.h)
 };
 // what one render writes (ctf_observe's arguments) ...
 struct RenderArgs {

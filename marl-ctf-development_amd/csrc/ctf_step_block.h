@@ -6,6 +6,8 @@
 #include <type_traits>
 
 #include "ctf_ring_dev.h"  // WAVE, u32x4_t (and through it ctf_step_core.h)
+#include "ctf_meta.h"      // the metadata rows a step block writes (META)
+#include "ctf_launch.h"    // StepArgs
 
 #ifndef STEP_STAMP
 #define STEP_STAMP(k) do { } while (0)
@@ -40,13 +42,22 @@ __device__ __forceinline__ void step_publish(const StepPub& pub, int sb, int lan
     if (lane == 0) st_sc1(pub.flags + sb, pub.value);
 }
 
+// where a step block's metadata rows go (META): f16 [E][N][M], and ctf_meta.h's reciprocal of an env's 8-byte chunks
+struct StepMeta {
+    uint16_t* out;
+    uint32_t chunk_div;
+};
+static inline StepMeta step_meta(const DevCfg& cfg, const StepArgs& a) { return StepMeta{a.meta, a.meta ? meta_chunk_div(cfg.N, cfg.M) : 0u}; }
+
 // The step of the EPW envs of step block sb (k_step, and the step blocks of k_step_observe).  PUBLISH (k_step_observe): the
 // grids and records leave write-through and the block's flag follows them (StepPub).  DIRECT: the streams of
-// CTF_RNG_COUNTER_DIRECT (ctf_step_core.h) in place of the rings' digest windows.
-template <bool METRICS, int W, bool PUBLISH, bool DIRECT = false>
+// CTF_RNG_COUNTER_DIRECT (ctf_step_core.h) in place of the rings' digest windows.  META: the wave also writes its envs' metadata
+// rows, made from the final records while they are in LDS (ctf_meta.h) — a template argument, so that the kernels without it are
+// instruction for instruction what they were: k_step<true, 4> is short of registers as it is.
+template <bool METRICS, int W, bool PUBLISH, bool DIRECT = false, bool META = false>
 __device__ __forceinline__ void step_block(const DevCfg& cfg, const DevPtrs& p, const int8_t* __restrict__ actions, float* __restrict__ rw32,
                                            double* __restrict__ rw64, uint8_t* __restrict__ done_out, uint32_t flags, int sb, int lane,
-                                           uint32_t* lds, const StepPub& pub) {
+                                           uint32_t* lds, const StepPub& pub, const StepMeta& sm = StepMeta{nullptr, 0u}) {
     constexpr int EPW = WAVE / W;  // envs per wave
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int g = lane / W, j = lane % W;
@@ -149,6 +160,15 @@ __device__ __forceinline__ void step_block(const DevCfg& cfg, const DevPtrs& p, 
     STEP_LDS_SYNC();
     STEP_STAMP(2);
 
+    // ---- the metadata values of the wave's envs, flat over the lanes (one f64 division sequence per 64 (env, value) pairs, where
+    // the render spent one per env), parked in each slot's action and digest-window bytes: the step is through with those
+    const MetaSlots mslots = {(uint8_t*)lds, SLB, cfg.GS, cfg.GS + cfg.RS};
+    static_assert(2 * META_MV_COUNT <= 4 * (4 + STEP_RNG_WORDS), "an env's metadata values do not fit its slot's dead words");
+    if constexpr (META) {
+        meta_park_fracs(cfg, mslots, nvalid, lane, WAVE);
+        meta_park_agents(cfg, mslots, nvalid, lane, WAVE);
+    }
+
     // ---- write the envs back (flat, coalesced 16-byte stores)
     {
         u32x4* gdst = (u32x4*)(p.grid + (size_t)env0 * cfg.GS);
@@ -170,6 +190,10 @@ __device__ __forceinline__ void step_block(const DevCfg& cfg, const DevPtrs& p, 
             else rdst[q] = v;
         }
         if (PUBLISH) step_publish(pub, sb, lane);
+        if constexpr (META) {  // the rows: every element one of the parked values (which one: meta_lut), 8 bytes per lane and pass
+            STEP_LDS_SYNC();
+            meta_gather_store(cfg, mslots, p.meta_lut, sm.chunk_div, nvalid, lane, WAVE, sm.out + (size_t)env0 * N * cfg.M);
+        }
         if (METRICS && !(STEP_ABLATE & 32)) {
             // this step's u8 deltas are added to the i32 counters with no-return atomics (nothing to wait for); two
             // neighbouring counters share one 64-bit add (a counter never carries out of its 32 bits)

@@ -11,6 +11,10 @@ Variants, all on the same handle and the same buffer (switched with ctf_obs_reta
   rebuild-nt  the same with the nontemporal hint
   direct      the buffer retained, k_observe_delta with the slot images kept in the shadow and carried forward, plain stores
   direct-nt   the same with the nontemporal hint
+  step-meta   direct-nt with the metadata rows written by k_step (CTF_STEP_META=1, the default; read at every ctf_step_observe)
+  render-meta direct-nt with the rows made by the render, as before round 15 (CTF_STEP_META=0)
+(every other variant runs with CTF_STEP_META unset.  The switch only changes ctf_step_observe, so it shows in the window of
+step_observe calls and not in the two kernels timed apart, which are ctf_step and ctf_observe.)
 Per round and variant: k_step and the render timed apart with events (the step of a variant runs behind that variant's render,
 so what the render leaves in the caches shows in it), then 100 back-to-back step_observe calls timed as one window.
 
@@ -54,7 +58,10 @@ def select(variant):
     if variant == "full":
         vec._call("ctf_obs_retain", None, vec._stream())
     else:
-        os.environ["CTF_OBS_DELTA_NT"] = "1" if variant.endswith("-nt") else "0"
+        os.environ.pop("CTF_STEP_META", None)
+        if variant in ("step-meta", "render-meta"):
+            os.environ["CTF_STEP_META"] = "1" if variant == "step-meta" else "0"
+        os.environ["CTF_OBS_DELTA_NT"] = "1" if variant.endswith("-nt") or variant.endswith("-meta") else "0"
         os.environ["CTF_OBS_DELTA_BITMAP"] = "1" if variant.startswith("delta") else "0"
         os.environ["CTF_OBS_DELTA_REBUILD"] = "1" if variant.startswith("rebuild") else "0"
         vec._call("ctf_obs_retain", _abi.ptr(buf), vec._stream())
@@ -84,7 +91,7 @@ def window(reps=100):
 
 VARIANTS = ("full", "delta", "delta-nt", "rebuild", "rebuild-nt", "direct", "direct-nt")
 if len(sys.argv) > 4:
-    assert set(sys.argv[4].split(",")) <= set(VARIANTS), sys.argv[4]
+    assert set(sys.argv[4].split(",")) <= set(VARIANTS + ("step-meta", "render-meta")), sys.argv[4]
     VARIANTS = tuple(sys.argv[4].split(","))
 for v in VARIANTS:
     select(v)
