@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states and ctf_import_states are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states and ctf_scripted_actions are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -437,6 +437,27 @@ int ctf_status(ctf_env* env, uint32_t* out_bits, void* stream);
  * key = (seed lo, seed hi), counter = (global env index = env_offset + e, step, 0, 0). */
 int ctf_random_actions(ctf_env* env, int8_t* actions_dev, uint64_t seed, uint32_t step,
                        uint32_t env_offset, void* stream);
+
+/* Scripted opponents: a baseline policy computed on the device from the env STATE (not from an observation), so that an evaluation
+ * or a league has a fixed anchor that plays at the env's speed and is reproducible bit for bit.  kind:
+ *   CTF_SCRIPT_RUNNER  a flag runner.  Agent a of team t heads for T = flag_pos[t] if has_flag[a], else flag_pos[1 - t]: standing next
+ *     to T is what the pickup and capture rules test (gridworld_ctf.py:583-600).  Goal cells: the cells inside the grid within
+ *     Chebyshev distance 1 of T whose tile is OPEN (0).  d = breadth-first distance to the goal cells (d = 0) over OPEN cells with
+ *     4-neighbour unit moves; every other tile is a wall: blocks, destructibles, flags and every agent (the asking one included).
+ *     The action is the lowest-numbered of 0..3 (deltas (-1,0), (1,0), (0,1), (0,-1)) whose neighbour is inside the grid and has the
+ *     minimum finite d; if there is none, 4 (stay).  Actions 5..8 are never chosen, so every agent type's action mask is respected.
+ *     Exploration: w = Philox4x32-10(key = (seed lo, seed hi), counter = (env_offset + e, step, a, 0x424F5431)), ctf_random_actions'
+ *     Philox; if w[0] < epsilon_q32 the action is (w[1] * 5) >> 32, uniform on 0..4.  epsilon_q32 = 0 is the deterministic bot.
+ * The actions are ENV actions: they go to ctf_step as they are (a caller that maps its networks' team-1 actions through
+ * REVERSED_ACTION_MAP must not map these).
+ *   actions_dev  int8 [E][N]: written only for the agents whose bit is set in agent_mask; every other byte is left alone, so a caller
+ *                fills in its own agents' actions and the bot the rest, in place
+ * One kernel launch and nothing else (none for an empty mask): stream-ordered, no allocation, no synchronisation, capturable behind
+ * ctf_step.  Works in every rng_mode and with log_metrics == 0; env state is only read and the env's generators are not touched.
+ * CTF_E_INVALID, before anything is launched: an unknown kind, a mask bit at or above N, a NULL actions_dev. */
+#define CTF_SCRIPT_RUNNER 0u
+int ctf_scripted_actions(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint32_t kind, uint32_t epsilon_q32,
+                         uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

@@ -30,6 +30,8 @@ RNG_MT19937 = 0
 RNG_COUNTER = 1
 RNG_COUNTER_DIRECT = 2  # the tape of RNG_COUNTER with nothing stored: 32 bytes of RNG state per env
 REVERSE_DEFAULT = 0xFFFFFFFF
+SCRIPT_RUNNER = 0  # ctf_scripted_actions' kinds
+SCRIPT_KINDS = {"runner": SCRIPT_RUNNER}
 
 # order of ctf_state_view.metrics rows == the reference's "agent_*" metric names (gridworld_ctf.py:456-468)
 METRIC_NAMES = (
@@ -166,6 +168,7 @@ SYMBOLS = {
     "ctf_import_states": (C.c_int, [_P, C.POINTER(CtfStateArrays), _P, C.c_int32, _P]),
     "ctf_status": (C.c_int, [_P, C.POINTER(C.c_uint32), _P]),
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "ctf_scripted_actions": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),
     "ctf_abi_version": (C.c_int32, []),
     "ctf_sizeof_config": (C.c_int32, []),

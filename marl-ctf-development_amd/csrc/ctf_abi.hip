@@ -807,3 +807,15 @@ extern "C" int ctf_random_actions(ctf_env* h, int8_t* actions, uint64_t seed, ui
     HIP_TRY(ctf_launch_random_actions(h->d, actions, seed, step, env_offset, (hipStream_t)stream));
     return CTF_OK;
 }
+
+// ---- scripted opponents (ctf_scripted.h / ctf_scripted.hip) ----------------------------------------------------------------------
+extern "C" int ctf_scripted_actions(ctf_env* h, int8_t* actions, uint32_t agent_mask, uint32_t kind, uint32_t epsilon_q32, uint64_t seed,
+                                    uint32_t step, uint32_t env_offset, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_scripted_actions: null handle");
+    if (!actions) return fail(CTF_E_INVALID, "ctf_scripted_actions: null actions");
+    if (kind != CTF_SCRIPT_RUNNER) return fail(CTF_E_INVALID, "ctf_scripted_actions: unknown kind %u", kind);
+    if (h->d.N < 32 && (agent_mask >> h->d.N)) return fail(CTF_E_INVALID, "ctf_scripted_actions: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_scripted_actions(script_args(h->d, h->p), actions, agent_mask, epsilon_q32, seed, step, env_offset, (hipStream_t)stream));
+    return CTF_OK;
+}

@@ -1,5 +1,5 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip and ctf_states.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip and ctf_scripted.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 
 #include "ctf_device.h"
 #include "ctf_harvest.h"
+#include "ctf_scripted.h"
 #include "ctf_snapshot.h"
 #include "ctf_states.h"
 #include "ctf_visitation.h"
@@ -66,4 +67,7 @@ hipError_t ctf_launch_visit_export(const VisitArgs&, const int32_t* idx, int n, 
 // ---- ctf_states.hip
 hipError_t ctf_launch_export_states(const StateShape&, const StateDev&, const int32_t* idx, int n, const StateArrays& out, hipStream_t);
 hipError_t ctf_launch_import_states(const StateShape&, const StateDev&, const StateArrays& in, const int32_t* idx, int n, hipStream_t);
+// ---- ctf_scripted.hip
+hipError_t ctf_launch_scripted_actions(const ScriptArgs&, int8_t* actions, uint32_t agent_mask, uint32_t epsilon_q32, uint64_t seed, uint32_t step,
+                                       uint32_t env_offset, hipStream_t);
 }

@@ -14,7 +14,9 @@ try:
     from .frames import StateRecorder, frames_to_trajectory
     from .harvest import EpisodeHarvest
     from .rollout import BatchedRolloutCollector
+    from .scripted import ScriptedPolicy
 except ImportError:  # pragma: no cover
+    from scripted import ScriptedPolicy
     from frames import StateRecorder, frames_to_trajectory
     from harvest import EpisodeHarvest
     from rollout import BatchedRolloutCollector
@@ -55,7 +57,8 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False, 
     int64 numpy [A, B, N, G, G]: each pairing's visitation maps summed over its envs, true counts, from one
     ``harvest_visitation(all_envs=True)`` beside the harvest.  ``record=k`` records the first k envs of every pairing's block (one
     ``frames.StateRecorder`` launch per step) and adds ``trajectories``, [A][B][k] dicts as ``duel_trajectory`` builds them; the
-    default makes no recorder, no key and no launch."""
+    default makes no recorder, no key and no launch.  Any entry of ``opponents`` may be a ``scripted.ScriptedPolicy``: it decides once per
+    step for the whole batch (one launch, no policy kernel) and its ENV actions reach ``step`` unmapped, in the rows of the envs it plays in."""
     import torch
 
     A, B, E = len(agents), len(opponents), vec.n_envs
@@ -87,10 +90,17 @@ def batched_tournament(vec, agents, opponents, max_steps=256, visitation=False, 
                 acts[sl][:, col.trained_idx] = col._policy(net, obs[sl], meta[sl], col.trained_idx)[0].to(torch.int8).transpose(0, 1)
             for b, net in enumerate(opponents):
                 rows = rows_of[b]
+                if isinstance(net, ScriptedPolicy):
+                    continue
                 act = col._policy(net, obs.index_select(0, rows), meta.index_select(0, rows), col.others_idx)[0]
                 acts[rows[:, None], col.others_idx[None, :]] = act.to(torch.int8).transpose(0, 1)
             mapped = col.rev_lut[acts.long()]  # team-1 agents act in their flipped view (utils.py:535-551)
-            vec.step(torch.where(col.is_team1[None, :], mapped, acts).contiguous())
+            joint = torch.where(col.is_team1[None, :], mapped, acts).contiguous()
+            for b, net in enumerate(opponents):
+                if isinstance(net, ScriptedPolicy):  # env actions: written behind the mapping
+                    rows = rows_of[b][:, None]
+                    joint[rows, col.others_idx[None, :]] = net.act(vec, col.others_mask)[rows, col.others_idx[None, :]]
+            vec.step(joint)
             if recorder:
                 recorder.record()
     harvest.update(all_envs=True)

@@ -389,6 +389,43 @@ class VecGridworldCtf:
         self._call("ctf_random_actions", a, int(seed), int(step), int(env_offset), self._stream())
         return out
 
+    def team_mask(self, team):
+        """The agent mask (bit i = agent i) of one team's agents."""
+        return sum(1 << i for i in range(self.N_AGENTS) if self.AGENT_TEAMS[i] == int(team))
+
+    def scripted_actions(self, agent_mask=None, team=None, out=None, epsilon=0.0, seed=0, step=None, kind="runner", env_offset=0):
+        """The scripted baseline's ENV actions (include/ctf_env.h, ctf_scripted_actions), computed on the device from the env state, for
+        the agents of ``agent_mask`` (bit i = agent i) or of ``team`` — exactly one of the two.  Written into ``out`` (int8 [E, N]) in
+        place: only the selected agents' bytes, every other byte is left alone, so a caller fills in its own agents' actions and the
+        bot the rest.  ``out=None`` uses a buffer this object owns (zero where never written).  The actions go to ``step`` as they are:
+        they are not view actions, nothing maps them through the flip.  ``epsilon``: probability of a uniform move on 0..4 instead,
+        drawn from Philox(seed; env_offset + e, step, agent); 0 is the deterministic bot.  ``step=None`` counts this object's calls that
+        left it to None (0, 1, 2, ...).  One launch, stream-ordered; the env's state and generators are only read / not touched."""
+        torch = _torch()
+        if (agent_mask is None) == (team is None):
+            raise ValueError("give agent_mask or team (one of them)")
+        if team is not None and int(team) not in (0, 1):
+            raise ValueError("team must be 0 or 1")
+        mask = int(agent_mask) if team is None else self.team_mask(team)
+        if mask < 0 or mask >> self.N_AGENTS:
+            raise ValueError(f"agent_mask 0x{mask:x} names an agent outside 0..{self.N_AGENTS - 1}")
+        if kind not in _abi.SCRIPT_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_abi.SCRIPT_KINDS)}")
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError("epsilon must be in [0, 1]")
+        if out is None:
+            if getattr(self, "_scripted_out", None) is None:
+                self._scripted_out = torch.zeros((self.n_envs, self.N_AGENTS), dtype=torch.int8, device=self.device)
+            out = self._scripted_out
+        if step is None:
+            step = getattr(self, "_scripted_calls", 0)
+            self._scripted_calls = step + 1
+        a = self._check_dev(out, torch.int8, self.n_envs * self.N_AGENTS)
+        eps_q32 = min(int(float(epsilon) * 4294967296.0), 0xFFFFFFFF)
+        self._call("ctf_scripted_actions", a, mask, _abi.SCRIPT_KINDS[kind], eps_q32, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+                   int(env_offset) & 0xFFFFFFFF, self._stream())
+        return out
+
     def counters(self):
         """-> (metrics int32 [E, 13, N] in _abi.METRIC_NAMES order, team_flag_captures int32 [E, 2], env_step_count int32 [E]):
         what utils.duel / MetricsLogger.harvest_metrics read from ``env.metrics``, for every env at once."""

@@ -25,9 +25,11 @@ import numpy as np
 try:
     from . import _abi
     from .gridworld_ctf import _REVERSED_ACTIONS
+    from .scripted import ScriptedPolicy
 except ImportError:  # pragma: no cover
     import _abi
     from gridworld_ctf import _REVERSED_ACTIONS
+    from scripted import ScriptedPolicy
 
 
 class BatchedRolloutCollector:
@@ -52,6 +54,7 @@ class BatchedRolloutCollector:
         self.A = n // 2  # the reference's num_agents_per_team
         if len(self.trained) != self.A:
             raise ValueError("teams must be balanced (the reference assumes N // 2 trained agents)")
+        self.others_mask = sum(1 << i for i in self.others)  # the agents a scripted opponent (scripted.py) decides for
         self.trained_idx = torch.tensor(self.trained, device=dev)
         self.others_idx = torch.tensor(self.others, device=dev)
         flag = {0: 1.0, 1: 1.0, 2: 0.0, 3: 0.0}  # AGENT_TYPE_ACTION_MASK (gridworld_ctf.py:218-223)
@@ -82,10 +85,11 @@ class BatchedRolloutCollector:
         # actions mapped back) as ONE launch (ctf_rollout_store_step) instead of ~17 small tensor kernels (0.15 of a 2.1 ms step)
         self.native_store = True
         self._store_args = None
+        self._no_other_act = None
 
     def use_codes(self, agent, opponent):
-        if self.compact is None:
-            return hasattr(agent, "act_from_codes") and hasattr(opponent, "act_from_codes")
+        if self.compact is None:  # (a scripted opponent reads the env state, no observation: the trained policy alone decides)
+            return hasattr(agent, "act_from_codes") and (isinstance(opponent, ScriptedPolicy) or hasattr(opponent, "act_from_codes"))
         return bool(self.compact)
 
     def _policy(self, net, obs, meta, idx):
@@ -154,8 +158,20 @@ class BatchedRolloutCollector:
 
     def joint_actions(self, agent, opponent, use_codes):
         """One decision of every agent of every env -> (what the trained team's policy returned, env actions int8 [E, N]):
-        team-1 agents' actions are mapped back through the flip (ppo.py:80-83,90-93)."""
+        team-1 agents' actions are mapped back through the flip (ppo.py:80-83,90-93).  A ``ScriptedPolicy`` opponent runs no policy
+        kernel: its agents' ENV actions are written into the joint action after the mapping, in place (one launch)."""
         torch, vec = self.torch, self.vec
+        if isinstance(opponent, ScriptedPolicy):
+            if use_codes:
+                codes, meta = vec.observe_codes()
+                trained = self._policy_codes(agent, codes, meta, self.trained_idx, self.trained)
+            else:
+                obs, meta = vec.observe()
+                trained = self._policy(agent, obs, meta, self.trained_idx)
+            env_act = self._env_actions
+            env_act[:, self.trained_idx] = trained[0].to(torch.int8).transpose(0, 1)
+            joint = torch.where(self.is_team1[None, :], self.rev_lut[env_act.long()], env_act).contiguous()
+            return trained, opponent.act(vec, self.others_mask, out=joint)
         if use_codes:
             codes, meta = vec.observe_codes()  # default reversal: team(i) == 1
             if (self.overlap_teams and agent is not opponent and codes.is_cuda and hasattr(agent, "_features_tuned")
@@ -192,7 +208,13 @@ class BatchedRolloutCollector:
                                     shared_t=one_team(self.trained), shared_o=one_team(self.others))
         sa = self._store_args
         a_act, a_lp, _, a_val = agent.act_from_codes(codes, meta, self.trained, sa["mask_t"], shared_view=sa["shared_t"], self_cells=vec.self_cells)
-        o_act = opponent.act_from_codes(codes, meta, self.others, sa["mask_o"], shared_view=sa["shared_o"], self_cells=vec.self_cells)[0]
+        scripted = isinstance(opponent, ScriptedPolicy)
+        if scripted:  # the store step wants a source for the other team's slots: zeros, overwritten below
+            if self._no_other_act is None:
+                self._no_other_act = torch.zeros((len(self.others) * E,), dtype=torch.int32, device=vec.device)
+            o_act = self._no_other_act
+        else:
+            o_act = opponent.act_from_codes(codes, meta, self.others, sa["mask_o"], shared_view=sa["shared_o"], self_cells=vec.self_cells)[0]
         i32 = lambda x: x.reshape(-1).to(torch.int32).contiguous()
         f32 = lambda x: x.reshape(-1).to(torch.float32).contiguous()
         a_act, o_act, a_lp, a_val = i32(a_act), i32(o_act), f32(a_lp), f32(a_val)
@@ -203,6 +225,8 @@ class BatchedRolloutCollector:
                   ptr(codes), ptr(meta), E, N, g * g, vec.META_LEN, sa["trained"], A, sa["others"], len(self.others), ptr(a_act), ptr(a_lp), ptr(a_val),
                   ptr(o_act), sa["lut"], sa["team1"], ptr(self.grid_codes[sl]), ptr(self.metadata_states[sl]), ptr(self.actions[sl]),
                   ptr(self.logprobs[sl]), ptr(self.values[sl]), ptr(self._env_actions), vec.device.index, _abi.stream_ptr(vec.device))
+        if scripted:  # ENV actions, behind the store step on the same stream: they are not mapped through the flip
+            opponent.act(vec, self.others_mask, out=self._env_actions)
 
     def preallocate(self, agent, opponent):
         """The observation part of the rollout buffer (29 GB of codes for 65 536 envs x 500 steps), allocated on the first collect

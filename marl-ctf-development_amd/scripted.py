@@ -1,0 +1,38 @@
+"""Scripted opponents: a baseline that sits where a network sits — the ``opponent`` of ``batched_duel``, any entry of
+``batched_tournament``'s ``opponents``, the ``opponent`` of ``BatchedRolloutCollector.collect`` — and is computed on the device
+from the env state by one launch (include/ctf_env.h, ctf_scripted_actions), so that a win rate has a fixed anchor and a league
+something to start against.
+
+A ``ScriptedPolicy`` is not a network: it has no ``get_action_and_value``, reads no observation and launches no policy kernel.  Its
+actions are ENV actions (the state is read, not a team-1 agent's flipped view): the collectors hand them to ``vec.step`` as they
+are, NOT through ``REVERSED_ACTION_MAP``.
+"""
+try:
+    from . import _abi
+except ImportError:  # pragma: no cover
+    import _abi
+
+
+class ScriptedPolicy:
+    """kind "runner": every agent takes a shortest open path to a cell next to the flag it wants — the other team's, or its own once
+    it carries one — (breadth-first over open cells; agents, flags and blocks are walls; ties go to the lowest action).
+    ``epsilon``: probability of a uniform move on 0..4 instead, from a Philox stream keyed by ``seed`` and indexed by (env, call,
+    agent): the same object replays the same games after ``restart()``."""
+
+    def __init__(self, kind="runner", epsilon=0.0, seed=0):
+        if kind not in _abi.SCRIPT_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_abi.SCRIPT_KINDS)}")
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError("epsilon must be in [0, 1]")
+        self.kind, self.epsilon, self.seed = kind, float(epsilon), int(seed)
+        self.calls = 0  # the exploration stream's step index: one per decision
+
+    def restart(self):
+        self.calls = 0
+
+    def act(self, vec, agent_mask, out=None, env_offset=0):
+        """One decision of the agents of ``agent_mask`` in every env of ``vec``, written into ``out`` (int8 [E, N]) in place."""
+        out = vec.scripted_actions(agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls, kind=self.kind,
+                                   env_offset=env_offset)
+        self.calls += 1
+        return out

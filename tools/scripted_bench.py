@@ -1,0 +1,113 @@
+"""What the scripted opponent costs next to the step: ctf_scripted_actions at 65 536 8_arena envs in bench state (phases staggered
+as bench.py staggers them), warm, in ONE process, the variants interleaved call by call (the A/B form of tools/harvest_bench.py):
+
+  launch  k_step (the yardstick), and the scripted launch for all eight agents and for one team, with epsilon 0 and 0.1
+  duel    a 500-step batched_duel of CtfPolicyNative against the bot, against the same duel between two native networks
+
+HIP-event time per call, medians over --calls calls after warm-up, --reps repetitions; the duels by the host clock round a device
+synchronise.  One JSON document on stdout (and --out).
+
+    python tools/scripted_bench.py --out profiles/r16_scripted_bench.json
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--duel-steps", type=int, default=500)
+    ap.add_argument("--duel-reps", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    import bench
+
+    pkg = importlib.import_module("marl-ctf-development_amd")
+    kw = dict(pkg.configs.ARENA_KWARGS, SCENARIO=pkg.CtfScenarios.arena_iii)
+    E = args.envs
+    seeds = np.arange(E, dtype=np.uint64) + 1
+    vec = pkg.VecGridworldCtf(E, device=0, py_seeds=seeds, np_seeds=seeds, tune_placement=False, **kw)
+    dev, gs, N = vec.device, int(vec.cfg.game_steps), vec.N_AGENTS
+    acts = torch.empty((E, N), dtype=torch.int8, device=dev)
+    bot_acts = torch.zeros((E, N), dtype=torch.int8, device=dev)
+    step_no = [0]
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        return a, b
+
+    def next_actions():
+        vec.random_actions(acts, seed=0xBE7C, step=step_no[0])
+        step_no[0] += 1
+
+    all_mask, team1 = (1 << N) - 1, vec.team_mask(1)
+    variants = {
+        "k_step": lambda: vec.step(acts, auto_reset=True),
+        "scripted_all_eps0": lambda: vec.scripted_actions(agent_mask=all_mask, out=bot_acts),
+        "scripted_team_eps0": lambda: vec.scripted_actions(agent_mask=team1, out=bot_acts),
+        "scripted_all_eps0.1": lambda: vec.scripted_actions(agent_mask=all_mask, out=bot_acts, epsilon=0.1, seed=1, step=step_no[0]),
+        "scripted_team_eps0.1": lambda: vec.scripted_actions(agent_mask=team1, out=bot_acts, epsilon=0.1, seed=1, step=step_no[0]),
+    }
+    bench.stagger_phases(vec, torch, 0, gs)
+    reps = []
+    for _ in range(args.reps):
+        events = {k: [] for k in variants}
+        for i in range(args.warmup + args.calls):
+            next_actions()
+            for k, fn in variants.items():  # k_step first: the scripted launches all see the state it left
+                ev = timed(fn)
+                if i >= args.warmup:
+                    events[k].append(ev)
+        torch.cuda.synchronize()
+        reps.append({k: statistics.median(a.elapsed_time(b) * 1e3 for a, b in v) for k, v in events.items()})
+    med = {k: statistics.median(r[k] for r in reps) for k in variants}
+    out = dict(envs=E, calls=args.calls, reps=args.reps, device=torch.cuda.get_device_name(0), unit="us per call",
+               launch=dict(medians_per_rep=reps, **med, ratio_to_k_step={k: med[k] / med["k_step"] for k in variants if k != "k_step"}))
+    assert vec.status() == 0
+
+    # the duels: one warm-up duel of a few steps each, then the timed ones, alternating
+    native = pkg.policy_native
+    nets = [native.CtfPolicyNative(9, vec.N_CHANNELS, vec.GRID_SIZE, vec.META_LEN, seed=s).cuda().prepare() for s in (1, 2)]
+    duels = {"native_vs_bot": lambda steps: pkg.batched_duel(vec, nets[0], pkg.ScriptedPolicy(), max_steps=steps - 1),
+             "native_vs_native": lambda steps: pkg.batched_duel(vec, nets[0], nets[1], max_steps=steps - 1)}
+    times = {k: [] for k in duels}
+    caps = {}
+    for k, fn in duels.items():
+        fn(8)
+    for _ in range(args.duel_reps):
+        for k, fn in duels.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn(args.duel_steps)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+            caps[k] = res["team_flag_captures"].sum(0).tolist()
+    out["duel"] = dict(steps=args.duel_steps, unit="s per duel", seconds=times, median={k: statistics.median(v) for k, v in times.items()},
+                       env_steps_per_s={k: E * args.duel_steps / statistics.median(v) for k, v in times.items()}, team_flag_captures=caps)
+    text = json.dumps(out, indent=1, default=str)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
