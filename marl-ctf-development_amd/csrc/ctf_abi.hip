@@ -440,6 +440,22 @@ extern "C" int32_t ctf_observe_retained(const ctf_env* h, const uint8_t* obs) {
     return retained_here(h, obs) ? 1 : 0;
 }
 
+// A test hook, deliberately not in include/ctf_env.h: the shadow copied out device to device, stream-ordered — grid u8 [E][GS],
+// pos u16 [E][CTF_MAX_AGENTS], key u32 [E], images u32 [E][4][obsc_image_dwords(CGG)]; NULL = not wanted.
+// tests/test_gpu_delta_planted.py compares the shadow a handle has carried forward over its steps with one built afresh.
+extern "C" int ctf_debug_obs_shadow(ctf_env* h, uint8_t* grid, uint16_t* pos, uint32_t* key, uint32_t* images, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "null handle");
+    if (!h->shadow.key) return fail(CTF_E_INVALID, "ctf_debug_obs_shadow: no buffer was ever retained");
+    DeviceScope guard(h->device);
+    const size_t E = (size_t)h->d.n_envs;
+    hipStream_t st = (hipStream_t)stream;
+    if (grid) HIP_TRY(hipMemcpyAsync(grid, h->shadow.grid, E * h->d.GS, hipMemcpyDeviceToDevice, st));
+    if (pos) HIP_TRY(hipMemcpyAsync(pos, h->shadow.pos, E * CTF_MAX_AGENTS * 2, hipMemcpyDeviceToDevice, st));
+    if (key) HIP_TRY(hipMemcpyAsync(key, h->shadow.key, E * 4, hipMemcpyDeviceToDevice, st));
+    if (images) HIP_TRY(hipMemcpyAsync(images, h->shadow.images, E * 16 * (size_t)obsc_image_dwords(h->d.CGG), hipMemcpyDeviceToDevice, st));
+    return CTF_OK;
+}
+
 extern "C" int32_t ctf_observe_kernel(const ctf_env* h, const uint8_t* obs) {
     if (!h) return -1;
     return ctf_observe_uses_tiles(h->d, obs) ? 1 : 0;

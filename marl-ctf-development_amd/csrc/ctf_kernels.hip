@@ -213,7 +213,8 @@ __host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
 #endif
 #define LGKM_ONLY 0xC07F  // s_waitcnt lgkmcnt(0): LDS traffic only — never drain the wave's outstanding stores
 // Profiling-only ablations (never defined in the shipped build; see tools/ablate.sh):
-//   bit0 no bit expansion, bit1 no chunk stores, bit2 no bitmap build, bit3 no metadata, bit4 metadata computed but not stored
+//   bit0 no bit expansion, bit1 no chunk stores, bit2 no bitmap build, bit3 no metadata, bit4 metadata computed but not stored,
+//   bit5 k_observe_delta's dirty-line list not compacted from the mask: an identity list of the same length (the wrong lines)
 #ifndef OBS_ABLATE
 #define OBS_ABLATE 0
 #endif
@@ -688,6 +689,13 @@ __global__ void __launch_bounds__(256) k_observe_delta_bitmap(DevCfg cfg, DevPtr
 //     (0.177 -> 0.156 ms; the carried images give 0.002).
 // (Compacting the mask 64 lines per pass with the mask's dwords as ballots, in place of the scan and the per-lane bit loop of
 // step 4, was built and measured too: it lost 0.005 ms and is not here.)
+// Round 17 (profiles/r17_delta_append.md): a moved viewer's two bytes come from the row and column bytes of both positions
+// (obsd_viewer_moved_rc: two divisions less per wave), every small product of the known-key path is a 24-bit multiply (OBSD_MUL:
+// 178 -> 10 quarter-rate integer multiplies in the kernel's text, the fdivs remain), and a lane works out where its image unit
+// lies once.  590 vector instructions per wave where there were 640, the same bytes.  The dirty-line list made by APPEND instead
+// of step 4's scan — a mark as an LDS atomicOr that returns the old dword, the lane that finds its bit clear taking a place with
+// an atomicAdd — was priced first (step 4 replaced by an identity list: 0.0037 ms, under the bar), built all the same, passed
+// every test and was 0.008 ms SLOWER in every round: two dependent LDS round trips per mark where the scan has none.  Not here.
 // `all_dirty` (CTF_OBS_DELTA_ALL_DIRTY=1, tests and soaks): every line is rewritten although the key is known, the images still
 // carried forward — every byte of the buffer then shows what the retained images hold.
 // Per-wave LDS: [rec RS][mvals 96][meta staging][slot images 4 x][own cells u16[16]][changed cells u32[GS]][line mask][line list u16].
@@ -760,13 +768,17 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     n_iu *= IU;
     auto image_unit = [&](int q) {
         const int k = (q >= IU) + (q >= 2 * IU) + (q >= 3 * IU);
-        return q + ((int)((slot_of_rank >> (4 * k)) & 3u) - k) * IU;
+        return q + OBSD_MUL((int)((slot_of_rank >> (4 * k)) & 3u) - k, IU);
     };
     u32x4_t img[OBS_DELTA_IMG_REGS];
+    int img_at[OBS_DELTA_IMG_REGS];  // where the unit lies in the env's [4][IU], shadow and LDS alike: worked out once
     if (!REBUILD) {
 #pragma unroll
         for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
-            if (n_iu > WAVE * j) img[j] = ((const u32x4_t*)ish)[image_unit(min(lane + WAVE * j, n_iu - 1))];  // (uniform condition)
+            if (n_iu > WAVE * j) {  // (uniform condition)
+                img_at[j] = image_unit(min(lane + WAVE * j, n_iu - 1));
+                img[j] = ((const u32x4_t*)ish)[img_at[j]];
+            }
     }
     const bool build = REBUILD || !known;  // uniform
 
@@ -778,7 +790,7 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
     } else if (!REBUILD) {
 #pragma unroll
         for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
-            if (lane + WAVE * j < n_iu) ((u32x4_t*)images)[image_unit(lane + WAVE * j)] = img[j];
+            if (lane + WAVE * j < n_iu) ((u32x4_t*)images)[img_at[j]] = img[j];  // (not clamped for such a lane)
         for (int q = lane + WAVE * OBS_DELTA_IMG_REGS; q < n_iu; q += WAVE)  // larger shapes: the rest, loaded here
             ((u32x4_t*)images)[image_unit(q)] = ((const u32x4_t*)ish)[image_unit(q)];
     }
@@ -795,13 +807,13 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
             const int w = lane + WAVE * j;
             if (GW > WAVE * j) {  // uniform
                 const bool mine = w < GW;
-                int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - r * cfg.G;
+                int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - OBSD_MUL(r, cfg.G);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int cell = 4 * w + q;
                     if (mine && cell < cfg.GG)
                         obsc_build_cell(s, used, cell, r, c, (cur[j] >> (8 * q)) & 0xFFu,
-                                        [&](int slot, int bit) { atomicOr(images + slot * IW + (bit >> 5), 1u << (bit & 31)); });
+                                        [&](int slot, int bit) { atomicOr(images + OBSD_MUL(slot, IW) + (bit >> 5), 1u << (bit & 31)); });
                     if (++c == cfg.G) { c = 0; r++; }
                 }
             }
@@ -847,15 +859,13 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
             if (ci < n_chg && i < N) {
                 const uint32_t ent = chg[ci];
                 const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
-                obsd_pair_changed_at(s, lead, ((reverse_mask >> i) & 1u) ? obsc_flip_rc(s, cell, r, cell - r * cfg.G) : cell, i, (ent >> 16) & 0xFFu,
-                                     ent >> 24, mark);
+                obsd_pair_changed_at(s, lead, ((reverse_mask >> i) & 1u) ? obsc_flip_rc(s, cell, r, cell - OBSD_MUL(r, cfg.G)) : cell, i,
+                                     (ent >> 16) & 0xFFu, ent >> 24, mark);
             }
         }
-        if (lane < N && cur_pos != old_pos) {
-            const int oc = (int)(int8_t)(old_pos & 0xFFu) * cfg.G + (int)(int8_t)(old_pos >> 8);
-            const int nc = (int)(int8_t)(cur_pos & 0xFFu) * cfg.G + (int)(int8_t)(cur_pos >> 8);
-            obsd_viewer_moved(s, reverse_mask, lead, lane, oc, nc, mark);
-        }
+        if (lane < N && cur_pos != old_pos)  // from the row and column bytes of both positions: no division (round 17)
+            obsd_viewer_moved_rc(s, reverse_mask, lead, lane, (int)(int8_t)(old_pos & 0xFFu), (int)(int8_t)(old_pos >> 8), (int)(int8_t)(cur_pos & 0xFFu),
+                                 (int)(int8_t)(cur_pos >> 8), mark);
         if (!REBUILD) {
             // the images follow the grid: a lane per (changed cell, slot) moves its bit, then stores the dwords it touched
             for (int at = 0; at < 4 * n_chg; at += WAVE) {
@@ -864,9 +874,9 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
                 if (ci < n_chg && (used & (1u << slot))) {
                     const uint32_t ent = chg[ci];
                     const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
-                    obsc_update_slot(s, slot, cell, r, cell - r * cfg.G, (ent >> 16) & 0xFFu, ent >> 24,
-                                     [&](int sl, int bit) { w_clear = sl * IW + (bit >> 5); atomicAnd(images + w_clear, ~(1u << (bit & 31))); },
-                                     [&](int sl, int bit) { w_set = sl * IW + (bit >> 5); atomicOr(images + w_set, 1u << (bit & 31)); });
+                    obsc_update_slot(s, slot, cell, r, cell - OBSD_MUL(r, cfg.G), (ent >> 16) & 0xFFu, ent >> 24,
+                                     [&](int sl, int bit) { w_clear = OBSD_MUL(sl, IW) + (bit >> 5); atomicAnd(images + w_clear, ~(1u << (bit & 31))); },
+                                     [&](int sl, int bit) { w_set = OBSD_MUL(sl, IW) + (bit >> 5); atomicOr(images + w_set, 1u << (bit & 31)); });
                 }
                 __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
                 __builtin_amdgcn_wave_barrier();
@@ -880,14 +890,27 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
 
     // ---- 4. compact: lane q lists the set bits of mask dword q behind those of the dwords before it
     uint32_t m = lane < ndw ? lmask[lane] : 0u;
-    int incl = __popc(m);
+    int total;
+    if (OBS_ABLATE & 32) {  // profiling only, the price of the compaction (profiles/r17_delta_append.md): as many lines, the wrong ones
+        uint32_t* cnt = (uint32_t*)llist;
+        if (lane == 0) *cnt = 0u;
+        if (m) atomicAdd(cnt, (uint32_t)__popc(m));
+        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+        __builtin_amdgcn_wave_barrier();
+        total = __builtin_amdgcn_readfirstlane((int)*cnt);
+        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
+        __builtin_amdgcn_wave_barrier();
+        for (int q = lane; q < total; q += WAVE) llist[q] = (uint16_t)q;
+    } else {
+        int incl = __popc(m);
 #pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int up = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += up;
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const int up = __shfl_up(incl, d, WAVE);
+            if (lane >= d) incl += up;
+        }
+        total = __shfl(incl, WAVE - 1, WAVE);
+        for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
     }
-    const int total = __shfl(incl, WAVE - 1, WAVE);
-    for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
     __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
     __builtin_amdgcn_wave_barrier();
     // ... and emit: lanes 8k .. 8k+7 hold the eight chunks of one line; chunks outside the env's own block belong to the
@@ -906,7 +929,7 @@ __global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, Ob
                 h[u] = 0u;
                 if (o[u] >= 0) {
                     const int view = (int)fdiv((uint32_t)o[u], cfg.div_cgg);
-                    h[u] = obsc_chunk_bits(s, reverse_mask, images, IW, selfc, view, o[u] - view * cfg.CGG);
+                    h[u] = obsc_chunk_bits(s, reverse_mask, images, IW, selfc, view, o[u] - OBSD_MUL(view, cfg.CGG));
                 }
             }
 #pragma unroll

@@ -39,17 +39,11 @@ OBSC_FN uint32_t obsc_slots_used(const ObsDeltaShape& s, uint32_t reverse_mask) 
 // dwords of one slot's image: CGG bits, one dword more for the second half of the last funnel read, in whole 16-byte units
 OBSC_FN int obsc_image_dwords(int CGG) { return (((CGG + 31) >> 5) + 1 + 3) & ~3; }
 
-// obsd_flip with the cell's row and column at hand
-OBSC_FN int obsc_flip_rc(const ObsDeltaShape& s, int cell, int r, int c) {
-    const int G = s.G;
-    if (s.flip_axis == -1) return s.GG - 1 - cell;
-    if (s.flip_axis == 0) return (G - 1 - r) * G + c;
-    if (s.flip_axis == 1) return r * G + (G - 1 - c);
-    return (G - 1 - c) * G + (G - 1 - r);
-}
+// obsd_flip with the cell's row and column at hand (ctf_obs_delta.h has the one definition)
+OBSC_FN int obsc_flip_rc(const ObsDeltaShape& s, int cell, int r, int c) { return obsd_flip_rc(s, cell, r, c); }
 // a viewer's own cell as its view shows it
 OBSC_FN int obsc_self_cell(const ObsDeltaShape& s, uint32_t reverse_mask, int i, int r, int c) {
-    const int cell = r * s.G + c;
+    const int cell = OBSD_MUL(r, s.G) + c;
     return ((reverse_mask >> i) & 1u) ? obsc_flip_rc(s, cell, r, c) : cell;
 }
 
@@ -63,8 +57,8 @@ OBSC_FN void obsc_build_cell(const ObsDeltaShape& s, uint32_t used, int cell, in
         if (!(used & (3u << (2 * t)))) continue;
         const uint32_t code = obsd_channel(s, t, v);
         if (code == CTF_OBS_CODE_NONE) continue;
-        if (used & (1u << (2 * t))) set(2 * t, (int)code * s.GG + cell);
-        if (used & (2u << (2 * t))) set(2 * t + 1, (int)code * s.GG + fl);
+        if (used & (1u << (2 * t))) set(2 * t, OBSD_MUL(code, s.GG) + cell);
+        if (used & (2u << (2 * t))) set(2 * t + 1, OBSD_MUL(code, s.GG) + fl);
     }
 }
 
@@ -77,8 +71,8 @@ OBSC_FN void obsc_update_slot(const ObsDeltaShape& s, int slot, int cell, int r,
     const uint32_t ca = a ? obsd_channel(s, slot >> 1, a) : CTF_OBS_CODE_NONE, cb = b ? obsd_channel(s, slot >> 1, b) : CTF_OBS_CODE_NONE;
     if (ca == cb) return;
     const int at = (slot & 1) ? obsc_flip_rc(s, cell, r, c) : cell;
-    if (ca != CTF_OBS_CODE_NONE) clear(slot, (int)ca * s.GG + at);
-    if (cb != CTF_OBS_CODE_NONE) set(slot, (int)cb * s.GG + at);
+    if (ca != CTF_OBS_CODE_NONE) clear(slot, OBSD_MUL(ca, s.GG) + at);
+    if (cb != CTF_OBS_CODE_NONE) set(slot, OBSD_MUL(cb, s.GG) + at);
 }
 // ... in every slot in `used` (k_observe_delta gives every (changed cell, slot) its own lane)
 template <class Clear, class Set>
@@ -90,7 +84,7 @@ OBSC_FN void obsc_update_cell(const ObsDeltaShape& s, uint32_t used, int cell, i
 // 16 bits of view i from its byte r on: its slot's image, and its own cell in plane 0.  Bits from CGG - r on are not the view's.
 OBSC_FN uint32_t obsc_view_bits(const ObsDeltaShape& s, uint32_t reverse_mask, const uint32_t* images, int image_dwords, const uint16_t* self,
                                 int i, int r) {
-    const uint32_t* q = images + obsc_slot(s, reverse_mask, i) * image_dwords + (r >> 5);
+    const uint32_t* q = images + OBSD_MUL(obsc_slot(s, reverse_mask, i), image_dwords) + (r >> 5);
     uint32_t h = (uint32_t)(((((uint64_t)q[1]) << 32) | q[0]) >> (r & 31));
     const uint32_t d = (uint32_t)((int)self[i] - r);
     if (d < 16u) h |= 1u << d;

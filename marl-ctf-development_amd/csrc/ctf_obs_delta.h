@@ -25,6 +25,16 @@
 #define OBSD_FN static inline
 #endif
 
+// A product of two small numbers — cells, rows, planes, views, slots, offsets into an env's block: every operand here is below
+// 2^18 (obsd_applies) — as ONE full-rate vector instruction on the device.  A 32-bit integer multiply (v_mul_lo_u32, and the
+// v_mad_u64_u32 the compiler likes for a multiply-add) issues at a quarter of the rate, and the known-key path of k_observe_delta ran
+// about 50 of them per wave (profiles/r17_delta_append.md); the 24-bit multiply gives the same product for operands of this size.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OBSD_MUL(a, b) __mul24((int)(a), (int)(b))
+#else
+#define OBSD_MUL(a, b) ((int)(a) * (int)(b))
+#endif
+
 #define CTF_OBS_LINE 128
 #define CTF_OBS_LINE_SHIFT 7
 #define CTF_OBS_DELTA_MAX_LINES 2048  // lines of one env's span the kernel's mask holds (64 lanes x 32 bits)
@@ -83,9 +93,9 @@ OBSD_FN void obsd_pair_changed_at(const ObsDeltaShape& s, int lead, int shown, i
     const int t = (int)((s.team_mask >> i) & 1u);
     const uint32_t ca = obsd_channel(s, t, a), cb = obsd_channel(s, t, b);
     if (ca == cb) return;
-    const int at = lead + i * s.CGG + shown;
-    if (ca != 15u) mark((at + (int)ca * s.GG) >> CTF_OBS_LINE_SHIFT);
-    if (cb != 15u) mark((at + (int)cb * s.GG) >> CTF_OBS_LINE_SHIFT);
+    const int at = lead + OBSD_MUL(i, s.CGG) + shown;
+    if (ca != 15u) mark((at + OBSD_MUL(ca, s.GG)) >> CTF_OBS_LINE_SHIFT);
+    if (cb != 15u) mark((at + OBSD_MUL(cb, s.GG)) >> CTF_OBS_LINE_SHIFT);
 }
 template <class Mark>
 OBSD_FN void obsd_pair_changed(const ObsDeltaShape& s, uint32_t reverse_mask, int lead, int cell, int i, uint32_t a, uint32_t b, Mark mark) {
@@ -99,6 +109,23 @@ OBSD_FN void obsd_viewer_moved(const ObsDeltaShape& s, uint32_t reverse_mask, in
     const int at = lead + i * s.CGG;
     mark((at + (rev ? obsd_flip(s, old_cell) : old_cell)) >> CTF_OBS_LINE_SHIFT);
     mark((at + (rev ? obsd_flip(s, new_cell) : new_cell)) >> CTF_OBS_LINE_SHIFT);
+}
+
+// obsd_flip with the cell's row and column at hand: no division
+OBSD_FN int obsd_flip_rc(const ObsDeltaShape& s, int cell, int r, int c) {
+    const int G = s.G;
+    if (s.flip_axis == -1) return s.GG - 1 - cell;
+    if (s.flip_axis == 0) return OBSD_MUL(G - 1 - r, G) + c;
+    if (s.flip_axis == 1) return OBSD_MUL(r, G) + (G - 1 - c);
+    return OBSD_MUL(G - 1 - c, G) + (G - 1 - r);
+}
+// obsd_viewer_moved from the (row, column) of both cells, as the position bytes give them: the same two marks
+template <class Mark>
+OBSD_FN void obsd_viewer_moved_rc(const ObsDeltaShape& s, uint32_t reverse_mask, int lead, int i, int old_r, int old_c, int new_r, int new_c, Mark mark) {
+    const bool rev = (reverse_mask >> i) & 1u;
+    const int at = lead + OBSD_MUL(i, s.CGG), oc = OBSD_MUL(old_r, s.G) + old_c, nc = OBSD_MUL(new_r, s.G) + new_c;
+    mark((at + (rev ? obsd_flip_rc(s, oc, old_r, old_c) : oc)) >> CTF_OBS_LINE_SHIFT);
+    mark((at + (rev ? obsd_flip_rc(s, nc, new_r, new_c) : nc)) >> CTF_OBS_LINE_SHIFT);
 }
 
 // A wave's ballot made into an ascending list, 64 items per pass (k_observe_delta gathers the changed cells so): in pass p lane L
