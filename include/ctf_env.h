@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states, ctf_import_states and ctf_scripted_actions are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions and ctf_scripted_roles are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -458,6 +458,30 @@ int ctf_random_actions(ctf_env* env, int8_t* actions_dev, uint64_t seed, uint32_
 #define CTF_SCRIPT_RUNNER 0u
 int ctf_scripted_actions(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint32_t kind, uint32_t epsilon_q32,
                          uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
+
+/* Scripted opponents with a ROLE per agent: nibble i of role_pack is agent i's role, so one team can mix them.  With opp(t) = every
+ * agent of the other team that stands inside the grid (by the team bits, whatever agent_mask says) and dil(S) = the cells inside the
+ * grid within Chebyshev distance 1 of a member of S, agent a of team t plays
+ *   CTF_ROLE_RUNNER  as CTF_SCRIPT_RUNNER above.
+ *   CTF_ROLE_CHASER  Tagging is automatic: an agent with damage > 0 hits every opponent within Chebyshev distance 1 at the end of its
+ *     turn (gridworld_ctf.py:796-837).  S = opp(t).  If a's own cell is in dil(S): 4, it tags already.  Otherwise the runner's search
+ *     and choice of action with the goal cells dil(S) & OPEN: the opponent nearest by PATH decides.
+ *   CTF_ROLE_GUARD   S = the members of opp(t) that carry a flag; if nobody does, the members within Chebyshev distance
+ *     CTF_GUARD_ZONE of flag_pos[t] (the reference's DEFENSIVE_ZONE_DISTANCE, gridworld_ctf.py:87, :882, and the zone in which a
+ *     guardian hits harder, GUARDIAN_DEFENSE_DISTANCE, :226, :808-810).  S not empty: the chaser's rule on S.  S empty: within
+ *     Chebyshev distance 1 of flag_pos[t] 4, otherwise the runner's search towards flag_pos[t].
+ * An agent that carries a flag acts as the runner does, whatever its role.  Exploration is ctf_scripted_actions' rule bit for bit (the
+ * same key, counter and tag), applied last; actions 5..8 are never produced.  actions_dev, the stream order and what is read are as for
+ * ctf_scripted_actions: one kernel launch and nothing else (none for an empty mask), capturable.  A role_pack whose asked agents are
+ * all runners launches ctf_scripted_actions' kernel.
+ * CTF_E_INVALID, before anything is launched: a nibble above CTF_ROLE_GUARD, a non-zero nibble at or above N, a mask bit at or above
+ * N, a NULL actions_dev. */
+#define CTF_ROLE_RUNNER 0u
+#define CTF_ROLE_CHASER 1u
+#define CTF_ROLE_GUARD 2u
+#define CTF_GUARD_ZONE 3
+int ctf_scripted_roles(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t epsilon_q32,
+                       uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

@@ -1,5 +1,5 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip and ctf_scripted.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip and ctf_scripted_roles.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,4 +70,7 @@ hipError_t ctf_launch_import_states(const StateShape&, const StateDev&, const St
 // ---- ctf_scripted.hip
 hipError_t ctf_launch_scripted_actions(const ScriptArgs&, int8_t* actions, uint32_t agent_mask, uint32_t epsilon_q32, uint64_t seed, uint32_t step,
                                        uint32_t env_offset, hipStream_t);
+// ---- ctf_scripted_roles.hip (all asked agents runners: ctf_launch_scripted_actions)
+hipError_t ctf_launch_scripted_roles(const ScriptArgs&, int8_t* actions, uint32_t agent_mask, uint64_t role_pack, uint32_t epsilon_q32, uint64_t seed,
+                                     uint32_t step, uint32_t env_offset, hipStream_t);
 }

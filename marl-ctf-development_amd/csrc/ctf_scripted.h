@@ -1,6 +1,7 @@
-// ctf_scripted.h — the scripted opponents (ctf_scripted_actions, ctf_scripted.hip): the policy, defined once as plain inline
-// functions that compile for the host and the device.  The kernel calls them with one lane per grid ROW; scr_env_actions below walks
-// the same functions over an array of rows, one env at a time (the host test, tests/scripted/scripted_main.cpp).
+// ctf_scripted.h — the scripted opponents (ctf_scripted_actions, ctf_scripted.hip; ctf_scripted_roles, ctf_scripted_roles.hip): the
+// policies, defined once as plain inline functions that compile for the host and the device.  The kernels call them with one lane per
+// grid ROW; scr_env_actions / scr_env_roles below walk the same functions over an array of rows, one env at a time (the host tests,
+// tests/scripted/scripted_main.cpp and roles_main.cpp).  The runner first; the ROLES (runner, chaser, guard per agent) further down.
 //
 // CTF_SCRIPT_RUNNER, agent a of team t, a pure function of the env state (grid, positions, has_flag) and the config:
 //   target   T = flag_pos[t] if has_flag[a], else flag_pos[1 - t]: standing next to T is what the pickup and capture rules test
@@ -112,6 +113,24 @@ CTF_HD uint32_t scr_asker(const ScriptArgs& A, const uint8_t* rec, int i, uint32
     return mine ? (uint32_t)pr | (uint32_t)pc << 8 | fl << 16 | 1u << 17 : 0u;
 }
 
+// the searches of one field over an array of rows: askers P, goal cells f (taken over as the first frontier) -> what every row keeps
+static inline void scr_rows_search(const uint32_t* open, int G, const uint32_t* P, uint32_t* f, ScrPick* k) {
+    uint32_t seen[32];
+    for (int r = 0; r < 32; r++) seen[r] = f[r], k[r] = ScrPick{0, 0, 0};
+    for (int n = 0; n < G * G; n++) {
+        uint32_t next[32], left = 0, alive = 0;
+        for (int r = 0; r < 32; r++) {
+            const uint32_t up = r > 0 ? f[r - 1] : 0u, down = r < 31 ? f[r + 1] : 0u;
+            scr_pick(k[r], P[r], f[r], up, down);
+            left |= P[r] & ~k[r].dec;
+            next[r] = scr_step(f[r], up, down, open[r], seen[r]);
+        }
+        if (!left) break;
+        for (int r = 0; r < 32; r++) seen[r] |= next[r], f[r] = next[r], alive |= next[r];
+        if (!alive) break;
+    }
+}
+
 // One env, rows as an array: out[i] for the agents of agent_mask, every other byte of out untouched.  `env` is the env's GLOBAL
 // index (env_offset + e).  An asker outside the grid (no valid state has one) stays.
 static inline void scr_env_actions(const ScriptArgs& A, const uint8_t* grid, const uint8_t* rec, uint32_t agent_mask, uint32_t epsilon_q32,
@@ -122,7 +141,7 @@ static inline void scr_env_actions(const ScriptArgs& A, const uint8_t* grid, con
         uint32_t ask[CTF_MAX_AGENTS];
         for (int i = 0; i < A.N; i++) ask[i] = scr_asker(A, rec, i, agent_mask, team);
         for (int carrying = 0; carrying < 2; carrying++) {
-            uint32_t P[32] = {0}, f[32], seen[32];
+            uint32_t P[32] = {0}, f[32];
             ScrPick k[32];
             bool any = false;
             for (int i = 0; i < A.N; i++)
@@ -130,19 +149,8 @@ static inline void scr_env_actions(const ScriptArgs& A, const uint8_t* grid, con
             if (!any) continue;
             int tr, tc;
             scr_target(A.flag_pack, team, carrying, tr, tc);
-            for (int r = 0; r < 32; r++) seen[r] = f[r] = scr_goal_row(open[r], r, tr, tc), k[r] = ScrPick{0, 0, 0};
-            for (int n = 0; n < A.G * A.G; n++) {
-                uint32_t next[32], left = 0, alive = 0;
-                for (int r = 0; r < 32; r++) {
-                    const uint32_t up = r > 0 ? f[r - 1] : 0u, down = r < 31 ? f[r + 1] : 0u;
-                    scr_pick(k[r], P[r], f[r], up, down);
-                    left |= P[r] & ~k[r].dec;
-                    next[r] = scr_step(f[r], up, down, open[r], seen[r]);
-                }
-                if (!left) break;
-                for (int r = 0; r < 32; r++) seen[r] |= next[r], f[r] = next[r], alive |= next[r];
-                if (!alive) break;
-            }
+            for (int r = 0; r < 32; r++) f[r] = scr_goal_row(open[r], r, tr, tc);
+            scr_rows_search(open, A.G, P, f, k);
             for (int i = 0; i < A.N; i++)
                 if ((ask[i] >> 17) && (int)((ask[i] >> 16) & 1u) == carrying) {
                     const ScrPick& q = k[ask[i] & 0xFFu];
@@ -154,5 +162,131 @@ static inline void scr_env_actions(const ScriptArgs& A, const uint8_t* grid, con
                 const int base = (ask[i] >> 17) ? out[i] : 4;
                 out[i] = (int8_t)scr_explore(base, epsilon_q32, seed, env, step, (uint32_t)i);
             }
+    }
+}
+
+// ---- ROLES (ctf_scripted_roles, ctf_scripted_roles.hip): nibble i of role_pack is agent i's role ------------------------------------
+// For agent a of team t; opp(t) = every agent of the other team inside the grid (the team bits, whatever agent_mask says), dil(S) = the
+// cells inside the grid within Chebyshev distance 1 of a member of S; "search with goals Q" is the runner's search and pick with Q for
+// the goal cells.  An agent that carries a flag acts as the runner does, whatever its role.
+//   CTF_ROLE_RUNNER  as above
+//   CTF_ROLE_CHASER  S = opp(t).  a's cell in dil(S): 4 (it tags already: tagging hits every opponent within Chebyshev distance 1,
+//                    gridworld_ctf.py:796-837).  Otherwise search with goals dil(S) & open: the opponent nearest by PATH wins.
+//   CTF_ROLE_GUARD   S = the carriers of opp(t); if there are none, the members of opp(t) within Chebyshev distance CTF_GUARD_ZONE of
+//                    flag_pos[t] (gridworld_ctf.py:87 DEFENSIVE_ZONE_DISTANCE, :226 and :808-810 GUARDIAN_DEFENSE_DISTANCE).  S not
+//                    empty: the chaser's rule on S.  S empty: within Chebyshev distance 1 of flag_pos[t] 4, else the runner's search
+//                    towards flag_pos[t].
+// Exploration is the runner's, applied last.  A (env, team) has up to four FIELDS, each a goal mask per row:
+//   0  own-flag window    carriers and posted guards (S empty); a posted guard next to the flag is decided before the search: 4
+//   1  other-flag window  runners that do not carry
+//   2  dil(opp)           chasers, minus those that stand in it
+//   3  dil(S)             guards when S is not empty, minus those that stand in it
+// "decided before the search" = the bit is taken out of the field's asker mask: an asker no search decides stays.
+#define SCR_FIELDS 4
+
+// what a row knows of the agents after one pass over them
+struct ScrRoles {
+    uint32_t carry, run, chase, guard;  // the asked agents of the team in this row: carrying; not carrying, by role
+    uint32_t opp, opp_carry, opp_zone;  // the opponents in this row: all; carrying; within CTF_GUARD_ZONE of the team's flag
+    uint32_t any;                       // the same in every row: bit 0 some opponent carries, bit 1 some opponent is in the zone
+};
+// agent i of this env, whoever it plays for: row | col << 8 | carrying << 16 | 1 << 17, or 0 outside the grid
+CTF_HD uint32_t scr_agent(const ScriptArgs& A, const uint8_t* rec, int i) {
+    const int pr = (int8_t)rec[A.off_pos + 2 * i], pc = (int8_t)rec[A.off_pos + 2 * i + 1];
+    const uint32_t fl = rec[A.off_flag + i] ? 1u : 0u;
+    return (pr >= 0 && pr < A.G && pc >= 0 && pc < A.G) ? (uint32_t)pr | (uint32_t)pc << 8 | fl << 16 | 1u << 17 : 0u;
+}
+CTF_HD uint32_t scr_role_of(uint64_t role_pack, int i) { return (uint32_t)(role_pack >> (4 * i)) & 15u; }
+// agent j (word v of scr_agent) as row r of `team` sees it
+CTF_HD void scr_roles_add(ScrRoles& m, const ScriptArgs& A, uint32_t v, int j, int r, int team, uint32_t agent_mask, uint64_t role_pack) {
+    const int pr = (int)(v & 0xFFu), pc = (int)((v >> 8) & 0xFFu);
+    const uint32_t in = v >> 17, carrying = (v >> 16) & 1u;
+    const uint32_t bit = (in && pr == r) ? 1u << (pc & 31) : 0u;
+    const bool theirs = (int)((A.team_mask >> j) & 1u) != team;
+    const bool asked = !theirs && ((agent_mask >> j) & 1u);
+    const int fr = (int)((A.flag_pack >> (16 * team)) & 0xFFu), fc = (int)((A.flag_pack >> (16 * team + 8)) & 0xFFu);
+    const int dr = pr > fr ? pr - fr : fr - pr, dc = pc > fc ? pc - fc : fc - pc;
+    const uint32_t zone = (in && dr <= CTF_GUARD_ZONE && dc <= CTF_GUARD_ZONE) ? 1u : 0u;
+    const uint32_t role = scr_role_of(role_pack, j);
+    const uint32_t obit = theirs ? bit : 0u, abit = asked ? bit : 0u, free_ = carrying ? 0u : abit;
+    m.opp |= obit;
+    m.opp_carry |= carrying ? obit : 0u;
+    m.opp_zone |= zone ? obit : 0u;
+    m.any |= theirs ? ((in & carrying) | zone << 1) : 0u;
+    m.carry |= carrying ? abit : 0u;
+    m.run |= role == CTF_ROLE_RUNNER ? free_ : 0u;
+    m.chase |= role == CTF_ROLE_CHASER ? free_ : 0u;
+    m.guard |= role == CTF_ROLE_GUARD ? free_ : 0u;
+}
+// the guards' set S, as a row mask
+CTF_HD uint32_t scr_guard_set(const ScrRoles& m) { return (m.any & 1u) ? m.opp_carry : m.opp_zone; }
+// row r of dil(S) from rows r - 1, r, r + 1 of S (0 outside the grid): h(up) | h(mid) | h(down), h(x) = x | x << 1 | x >> 1
+CTF_HD uint32_t scr_dil(uint32_t up, uint32_t mid, uint32_t down, int G, int r) {
+    const uint32_t x = up | mid | down;
+    return r < G ? (x | (x << 1) | (x >> 1)) & (G >= 32 ? 0xFFFFFFFFu : (1u << G) - 1u) : 0u;
+}
+// the askers P and goal cells `goal` of row r, per field
+CTF_HD void scr_role_fields(const ScrRoles& m, uint32_t open, int r, uint32_t flag_pack, int team, uint32_t dil_opp, uint32_t dil_set, uint32_t* P,
+                            uint32_t* goal) {
+    int fr, fc, tr, tc;
+    scr_target(flag_pack, team, 1, fr, fc);
+    scr_target(flag_pack, team, 0, tr, tc);
+    const uint32_t window = (r >= fr - 1 && r <= fr + 1) ? (uint32_t)((7ull << fc) >> 1) : 0u;  // next to the own flag (or on it)
+    const bool posted = (m.any & 3u) == 0u;                                                      // S is empty
+    P[0] = m.carry | (posted ? m.guard & ~window : 0u);
+    P[1] = m.run;
+    P[2] = m.chase & ~dil_opp;
+    P[3] = posted ? 0u : m.guard & ~dil_set;
+    goal[0] = scr_goal_row(open, r, fr, fc);
+    goal[1] = scr_goal_row(open, r, tr, tc);
+    goal[2] = dil_opp & open;
+    goal[3] = dil_set & open;
+}
+// the field agent (word v, role) asks
+CTF_HD int scr_role_field(uint32_t v, uint32_t role, uint32_t any) {
+    if ((v >> 16) & 1u) return 0;
+    return role == CTF_ROLE_RUNNER ? 1 : role == CTF_ROLE_CHASER ? 2 : (any & 3u) ? 3 : 0;
+}
+
+// scr_env_actions with roles
+static inline void scr_env_roles(const ScriptArgs& A, const uint8_t* grid, const uint8_t* rec, uint32_t agent_mask, uint64_t role_pack,
+                                 uint32_t epsilon_q32, uint64_t seed, uint32_t step, uint32_t env, int8_t* out) {
+    uint32_t open[32], word[CTF_MAX_AGENTS];
+    for (int r = 0; r < 32; r++) open[r] = scr_row_open(grid, A.G, A.GS, r);
+    for (int i = 0; i < A.N; i++) word[i] = scr_agent(A, rec, i);
+    for (int team = 0; team < 2; team++) {
+        if (!((script_teams(A, agent_mask) >> team) & 1u)) continue;
+        ScrRoles m[32];
+        uint32_t P[SCR_FIELDS][32], goal[SCR_FIELDS][32];
+        for (int r = 0; r < 32; r++) {
+            m[r] = ScrRoles{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int j = 0; j < A.N; j++) scr_roles_add(m[r], A, word[j], j, r, team, agent_mask, role_pack);
+        }
+        for (int r = 0; r < 32; r++) {
+            const uint32_t o_up = r > 0 ? m[r - 1].opp : 0u, o_down = r < 31 ? m[r + 1].opp : 0u;
+            const uint32_t s_up = r > 0 ? scr_guard_set(m[r - 1]) : 0u, s_down = r < 31 ? scr_guard_set(m[r + 1]) : 0u;
+            uint32_t p[SCR_FIELDS], g[SCR_FIELDS];
+            scr_role_fields(m[r], open[r], r, A.flag_pack, team, scr_dil(o_up, m[r].opp, o_down, A.G, r),
+                            scr_dil(s_up, scr_guard_set(m[r]), s_down, A.G, r), p, g);
+            for (int f = 0; f < SCR_FIELDS; f++) P[f][r] = p[f], goal[f][r] = g[f];
+        }
+        for (int i = 0; i < A.N; i++)
+            if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team) out[i] = 4;
+        for (int f = 0; f < SCR_FIELDS; f++) {
+            uint32_t any = 0;
+            for (int r = 0; r < 32; r++) any |= P[f][r];
+            if (!any) continue;
+            ScrPick k[32];
+            scr_rows_search(open, A.G, P[f], goal[f], k);
+            for (int i = 0; i < A.N; i++)
+                if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team && (word[i] >> 17) &&
+                    scr_role_field(word[i], scr_role_of(role_pack, i), m[0].any) == f) {
+                    const ScrPick& q = k[word[i] & 0xFFu];
+                    out[i] = (int8_t)scr_action(q.dec, q.b0, q.b1, (int)((word[i] >> 8) & 0xFFu));
+                }
+        }
+        for (int i = 0; i < A.N; i++)
+            if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team)
+                out[i] = (int8_t)scr_explore(out[i], epsilon_q32, seed, env, step, (uint32_t)i);
     }
 }

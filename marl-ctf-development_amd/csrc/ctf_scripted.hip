@@ -15,17 +15,7 @@
 
 #include "ctf_launch.h"
 #include "ctf_scripted.h"
-
-#define SCR_WAVE 64
-#define SCR_WPB 4  // waves per block
-
-// f of the lane below / above in the wave (0 at the wave's ends)
-__device__ __forceinline__ uint32_t scr_from_lower_lane(uint32_t f) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, 0x138 /* wave_shr:1 */, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t scr_from_upper_lane(uint32_t f) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, 0x130 /* wave_shl:1 */, 0xF, 0xF, true);
-}
+#include "ctf_scripted_dev.h"
 
 template <int W>
 __global__ void __launch_bounds__(SCR_WAVE* SCR_WPB) k_scripted_actions(ScriptArgs A, int8_t* actions, uint32_t agent_mask, uint32_t teams,

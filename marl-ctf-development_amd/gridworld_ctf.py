@@ -401,6 +401,35 @@ class VecGridworldCtf:
         they are not view actions, nothing maps them through the flip.  ``epsilon``: probability of a uniform move on 0..4 instead,
         drawn from Philox(seed; env_offset + e, step, agent); 0 is the deterministic bot.  ``step=None`` counts this object's calls that
         left it to None (0, 1, 2, ...).  One launch, stream-ordered; the env's state and generators are only read / not touched."""
+        if kind not in _abi.SCRIPT_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_abi.SCRIPT_KINDS)}")
+        return self._scripted("ctf_scripted_actions", _abi.SCRIPT_KINDS[kind], agent_mask, team, out, epsilon, seed, step, env_offset)
+
+    def role_pack(self, roles):
+        """``roles`` — a sequence of N names of _abi.SCRIPT_ROLES, or a dict agent -> name (the rest are runners) — as
+        ctf_scripted_roles' role_pack: nibble i is agent i's role."""
+        n = self.N_AGENTS
+        if isinstance(roles, dict):
+            if any(not isinstance(i, int) or not 0 <= i < n for i in roles):
+                raise ValueError(f"roles names an agent outside 0..{n - 1}")
+            names = [roles.get(i, "runner") for i in range(n)]
+        else:
+            names = list(roles)
+            if len(names) != n:
+                raise ValueError(f"roles must name {n} agents")
+        if any(name not in _abi.SCRIPT_ROLES for name in names):
+            raise ValueError(f"a role must be one of {sorted(_abi.SCRIPT_ROLES)}")
+        return sum(_abi.SCRIPT_ROLES[name] << (4 * i) for i, name in enumerate(names))
+
+    def scripted_roles(self, roles, agent_mask=None, team=None, out=None, epsilon=0.0, seed=0, step=None, env_offset=0):
+        """``scripted_actions`` with a ROLE per agent (include/ctf_env.h, ctf_scripted_roles): "runner" heads for the flag, "chaser"
+        for the opponent nearest by path until it stands within tagging reach of one, "guard" for an opponent that carries a flag
+        or has come within 3 cells of its own flag, and waits next to that flag otherwise.  ``roles``: a sequence of N names, or a
+        dict agent -> name with the rest runners; the roles of agents outside ``agent_mask`` / ``team`` are not used.  Everything
+        else is ``scripted_actions``'."""
+        return self._scripted("ctf_scripted_roles", self.role_pack(roles), agent_mask, team, out, epsilon, seed, step, env_offset)
+
+    def _scripted(self, call, what, agent_mask, team, out, epsilon, seed, step, env_offset):
         torch = _torch()
         if (agent_mask is None) == (team is None):
             raise ValueError("give agent_mask or team (one of them)")
@@ -409,8 +438,6 @@ class VecGridworldCtf:
         mask = int(agent_mask) if team is None else self.team_mask(team)
         if mask < 0 or mask >> self.N_AGENTS:
             raise ValueError(f"agent_mask 0x{mask:x} names an agent outside 0..{self.N_AGENTS - 1}")
-        if kind not in _abi.SCRIPT_KINDS:
-            raise ValueError(f"kind must be one of {sorted(_abi.SCRIPT_KINDS)}")
         if not 0.0 <= float(epsilon) <= 1.0:
             raise ValueError("epsilon must be in [0, 1]")
         if out is None:
@@ -422,8 +449,7 @@ class VecGridworldCtf:
             self._scripted_calls = step + 1
         a = self._check_dev(out, torch.int8, self.n_envs * self.N_AGENTS)
         eps_q32 = min(int(float(epsilon) * 4294967296.0), 0xFFFFFFFF)
-        self._call("ctf_scripted_actions", a, mask, _abi.SCRIPT_KINDS[kind], eps_q32, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
-                   int(env_offset) & 0xFFFFFFFF, self._stream())
+        self._call(call, a, mask, what, eps_q32, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(env_offset) & 0xFFFFFFFF, self._stream())
         return out
 
     def counters(self):

@@ -36,3 +36,28 @@ class ScriptedPolicy:
                                    env_offset=env_offset)
         self.calls += 1
         return out
+
+
+class ScriptedTeam(ScriptedPolicy):
+    """A bot with a ROLE per agent (``VecGridworldCtf.scripted_roles``): ``roles`` is a sequence of N names of "runner", "chaser" and
+    "guard", a dict agent -> name (the rest run), or a callable ``cfg -> roles`` resolved against ``vec.cfg`` at the first ``act``
+    (``guardians_guard`` below).  It sits wherever a ``ScriptedPolicy`` sits; the agents it decides for are the caller's
+    ``agent_mask``, so one object serves either team."""
+
+    def __init__(self, roles, epsilon=0.0, seed=0):
+        super().__init__("runner", epsilon, seed)
+        self.roles = roles
+        self._resolved = None
+
+    def act(self, vec, agent_mask, out=None, env_offset=0):
+        if self._resolved is None:
+            self._resolved = self.roles(vec.cfg) if callable(self.roles) else self.roles
+        out = vec.scripted_roles(self._resolved, agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls,
+                                 env_offset=env_offset)
+        self.calls += 1
+        return out
+
+
+def guardians_guard(cfg):
+    """roles for ``ScriptedTeam``: the agents of type 1 (guardians: they hit harder near their own flag) guard, the rest run"""
+    return ["guard" if int(cfg.agent_type[i]) == 1 else "runner" for i in range(cfg.n_agents)]

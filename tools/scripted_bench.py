@@ -2,12 +2,15 @@
 as bench.py staggers them), warm, in ONE process, the variants interleaved call by call (the A/B form of tools/harvest_bench.py):
 
   launch  k_step (the yardstick), and the scripted launch for all eight agents and for one team, with epsilon 0 and 0.1
+  roles   with --roles: ctf_scripted_roles for both teams and for one — an all-runner pack (ctf_scripted_actions' kernel: the same
+          time), all chasers, all guards, and the mix in which the guardians guard and the rest run — next to ctf_scripted_actions
   duel    a 500-step batched_duel of CtfPolicyNative against the bot, against the same duel between two native networks
 
 HIP-event time per call, medians over --calls calls after warm-up, --reps repetitions; the duels by the host clock round a device
 synchronise.  One JSON document on stdout (and --out).
 
     python tools/scripted_bench.py --out profiles/r16_scripted_bench.json
+    python tools/scripted_bench.py --roles --duel-reps 0 --out profiles/r18_scripted_roles_bench.json
 """
 import argparse
 import importlib
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--duel-steps", type=int, default=500)
     ap.add_argument("--duel-reps", type=int, default=2)
+    ap.add_argument("--roles", action="store_true", help="add the ctf_scripted_roles variants to the launch comparison")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -66,6 +70,11 @@ def main():
         "scripted_all_eps0.1": lambda: vec.scripted_actions(agent_mask=all_mask, out=bot_acts, epsilon=0.1, seed=1, step=step_no[0]),
         "scripted_team_eps0.1": lambda: vec.scripted_actions(agent_mask=team1, out=bot_acts, epsilon=0.1, seed=1, step=step_no[0]),
     }
+    if args.roles:
+        packs = {"runner": ["runner"] * N, "chaser": ["chaser"] * N, "guard": ["guard"] * N, "guardians_guard": pkg.scripted.guardians_guard(vec.cfg)}
+        for name, roles in packs.items():
+            variants[f"roles_all_{name}"] = lambda roles=roles: vec.scripted_roles(roles, agent_mask=all_mask, out=bot_acts)
+            variants[f"roles_team_{name}"] = lambda roles=roles: vec.scripted_roles(roles, agent_mask=team1, out=bot_acts)
     bench.stagger_phases(vec, torch, 0, gs)
     reps = []
     for _ in range(args.reps):
@@ -81,6 +90,9 @@ def main():
     med = {k: statistics.median(r[k] for r in reps) for k in variants}
     out = dict(envs=E, calls=args.calls, reps=args.reps, device=torch.cuda.get_device_name(0), unit="us per call",
                launch=dict(medians_per_rep=reps, **med, ratio_to_k_step={k: med[k] / med["k_step"] for k in variants if k != "k_step"}))
+    if args.roles:  # every role variant against the runner's launch for the same agents
+        out["launch"]["ratio_to_runner"] = {k: med[k] / med["scripted_all_eps0" if k.startswith("roles_all") else "scripted_team_eps0"]
+                                            for k in variants if k.startswith("roles_")}
     assert vec.status() == 0
 
     # the duels: one warm-up duel of a few steps each, then the timed ones, alternating
@@ -91,7 +103,8 @@ def main():
     times = {k: [] for k in duels}
     caps = {}
     for k, fn in duels.items():
-        fn(8)
+        if args.duel_reps:
+            fn(8)
     for _ in range(args.duel_reps):
         for k, fn in duels.items():
             torch.cuda.synchronize()
@@ -100,8 +113,9 @@ def main():
             torch.cuda.synchronize()
             times[k].append(time.perf_counter() - t0)
             caps[k] = res["team_flag_captures"].sum(0).tolist()
-    out["duel"] = dict(steps=args.duel_steps, unit="s per duel", seconds=times, median={k: statistics.median(v) for k, v in times.items()},
-                       env_steps_per_s={k: E * args.duel_steps / statistics.median(v) for k, v in times.items()}, team_flag_captures=caps)
+    if args.duel_reps:
+        out["duel"] = dict(steps=args.duel_steps, unit="s per duel", seconds=times, median={k: statistics.median(v) for k, v in times.items()},
+                           env_steps_per_s={k: E * args.duel_steps / statistics.median(v) for k, v in times.items()}, team_flag_captures=caps)
     text = json.dumps(out, indent=1, default=str)
     print(text)
     if args.out:
