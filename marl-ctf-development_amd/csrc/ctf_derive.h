@@ -47,7 +47,7 @@ static int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
 // Which of the env's distinct metadata values (mv[] of obs_build_env: 0 step fraction, 1 + t capture ratio for a viewer of
 // team t, 4 + j uint8-truncated hp of agent j, 20 + j has_flag[j], 40 = 1.0, 41 = 0.0) element k of viewer i's row shows
-// (gridworld_ctf.py:1044-1067) — the host twin of obs_meta_lut in ctf_kernels.hip, for the kernels that cannot afford to
+// (gridworld_ctf.py:1044-1067) — the host twin of obs_meta_lut in ctf_render_dev.h, for the kernels that cannot afford to
 // rebuild the table per wave.
 static void host_meta_lut(const DevCfg& d, uint8_t* out) {
     const int N = d.N, M = d.M;

@@ -11,6 +11,8 @@
 //   k_export_counters bulk export of the evaluation counters
 //   k_random_actions  synthetic Philox4x32-10 action stream for bench / tests
 // and their launchers (ctf_launch.h).  Seeding, the bulk ring refill and the generators' import / export: ctf_rng.hip.
+// The retained render (k_observe_delta, k_observe_delta_bitmap, k_obs_key_clear and their launchers) is ctf_observe_delta.hip, a
+// translation unit of its own: work on it leaves this file's code objects alone.  What both share: ctf_render_dev.h.
 //
 // Integer / byte work, HBM-bound: no MFMA anywhere.  Wavefront = 64 lanes is assumed throughout.
 #include <hip/hip_runtime.h>
@@ -19,8 +21,6 @@
 #include <type_traits>
 
 #include "ctf_launch.h"
-#include "ctf_obs_delta.h"
-#include "ctf_obs_chunk.h"
 // Profiling-only phase trace of the step kernel (tools/trace_step.py): lane 0 of every block stamps the 100 MHz wall clock at
 // fixed points (0 start, 1 staged, 7 hit bits, 5 ring, 6 shuffle 1, 8/9/10 + 3 k act / tagging / metrics of turn k, 32 turns
 // done, 33 shuffle 2, 34 stepped, 2 barrier, 3 written back, 4 end); never defined in the shipped build.
@@ -91,6 +91,7 @@ extern "C" int ctf_debug_step_trace(unsigned long long* host_out) {
 #endif
 
 #include "ctf_step_block.h"  // step_block: the staging, group_step and the write-back of one step block
+#include "ctf_render_dev.h"  // what the renders share (behind STEP_STAMP, like ctf_step_block.h, which it includes)
 
 #ifndef STEP_TAIL_PAIRS
 #define STEP_TAIL_PAIRS 16  // (env, stream) pairs a tail block looks after (ring regeneration)
@@ -182,26 +183,7 @@ k_step(DevCfg cfg, DevPtrs p, const int8_t* __restrict__ actions, float* __restr
 //      expanded to a byte (3 full-rate VALU ops per 4 bytes), one 1-KiB-aligned coalesced store
 //      instruction per 64 chunks.
 // Metadata rows (f16 [N][2N+6]) are assembled in LDS and leave as 8-byte stores.
-//
-// ---- The per-wave LDS of the three renders (bytes).  Each kernel carves its own up by these sizes, in this order:
-//   k_observe        [rec RS][mvals 96][meta staging][meta source LUT][bitmap]
-//   k_observe_codes  [rec RS][mvals 96][meta staging][meta source LUT][grid GS][self cell u16[16]][maps 4 x (GGp + 4)]
-//   tile_render      [bitmap TILE / 8][rec RS][mvals 96][meta staging]          (its LUT is the host-built table in global memory)
-#define OBS_MV_BYTES 96
-#define OBS_TILE CTF_OBS_TILE
-__host__ __device__ inline int obs_meta_stage_bytes(int N, int M) { return (N * M * 2 + 15) & ~15; }
-__host__ __device__ inline int obs_bitmap_bytes(int obs_bytes) { return ((((obs_bytes + 31) / 32 + 1) * 4) + 15) & ~15; }
-__host__ __device__ inline int obs_meta_lut_bytes(int N, int M) { return (N * M + 15) & ~15; }
-__host__ __device__ inline int codes_map_stride(int GG) { return ((GG + 3) & ~3) + 4; }  // + 4: the funnel read's second dword
-__host__ __device__ inline int obs_wave_bytes(int RS, int N, int M, int obs_bytes) {
-    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_meta_lut_bytes(N, M) + obs_bitmap_bytes(obs_bytes);
-}
-__host__ __device__ inline int codes_wave_bytes(int GS, int RS, int GG, int N, int M) {
-    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_meta_lut_bytes(N, M) + GS + 32 + 4 * codes_map_stride(GG);
-}
-__host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
-    return OBS_TILE / 8 + RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M);
-}
+// (The per-wave LDS sizes of the renders, expand4, flip_cell, obs_meta_lut and obs_build_env: ctf_render_dev.h.)
 
 #ifndef OBS_TILES_DEFAULT
 #define OBS_TILES_DEFAULT 1  // ctf_launch_observe takes the tile render whenever it applies (CTF_OBS_TILES=0 / 1 overrides)
@@ -211,30 +193,6 @@ __host__ __device__ inline int tiles_wave_bytes(int RS, int N, int M) {
 // arena envs it is 9 % SLOWER than the two launches (0.325 against 0.298 ms, profiles/r06_one_launch_step_observe.md)
 #define STEP_OBSERVE_ONE_LAUNCH_DEFAULT 0
 #endif
-#define LGKM_ONLY 0xC07F  // s_waitcnt lgkmcnt(0): LDS traffic only — never drain the wave's outstanding stores
-// Profiling-only ablations (never defined in the shipped build; see tools/ablate.sh):
-//   bit0 no bit expansion, bit1 no chunk stores, bit2 no bitmap build, bit3 no metadata, bit4 metadata computed but not stored,
-//   bit5 k_observe_delta's dirty-line list not compacted from the mask: an identity list of the same length (the wrong lines)
-#ifndef OBS_ABLATE
-#define OBS_ABLATE 0
-#endif
-
-template <int ALIGN>
-struct OutVec;
-template <>
-struct OutVec<16> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
-template <>
-struct OutVec<4> { typedef uint32_t type __attribute__((ext_vector_type(4), aligned(4))); };
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int flip_cell(const DevCfg& cfg, int cell, int r, int c) {
-    // destination of cell (r, c) under reverse_grid (gridworld_ctf.py:1003-1007)
-    const int G = cfg.G;
-    if (cfg.flip_axis == -1) return cfg.GG - 1 - cell;      // np.flip over both axes
-    if (cfg.flip_axis == 0) return (G - 1 - r) * G + c;     // np.flip(plane, 0)
-    if (cfg.flip_axis == 1) return r * G + (G - 1 - c);     // np.flip(plane, 1)
-    return (G - 1 - c) * G + (G - 1 - r);                   // np.rot90(plane.T, 2)
-}
 // A load the compiler does not track: issued one env ahead of its use, waited for by obs_prefetch_wait.
 // (vmcnt retires in issue order, so a compiler-placed wait for next env's state would first drain every
 // store of the current env; issued BEFORE those stores and waited for with a counted vmcnt a few
@@ -254,145 +212,6 @@ __device__ __forceinline__ uint32_t obs_prefetch_dword(const uint32_t* ptr) {
 // ... with vmcnt(8): the two prefetch loads are older than the >= OBS_PF_WAIT stores issued since
 #define OBS_PREFETCH_WAIT(a, b) asm volatile("s_waitcnt vmcnt(8)" : "+v"(a), "+v"(b)::"memory")
 #define OBS_PREFETCH_DRAIN(a, b) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b)::"memory")
-
-// 4 bits -> 4 bytes of 0/1: the four shifted copies of the nibble do not overlap, so no carries
-__device__ __forceinline__ uint32_t expand4(uint32_t h, int j) {
-    return (((h >> (4 * j)) & 15u) * 0x00204081u) & 0x01010101u;
-}
-
-struct ObsSlots {  // which agents look through each (viewer team, reversed?) view — uniform over the launch
-    uint32_t a[4];
-};
-__device__ __forceinline__ ObsSlots obs_slots(const DevCfg& cfg, uint32_t reverse_mask) {
-    ObsSlots s = {{0, 0, 0, 0}};
-    for (int i = 0; i < cfg.N; i++) {
-        const int sl = cfg.team[i] * 2 + (int)((reverse_mask >> i) & 1u);
-        s.a[0] |= (sl == 0) ? (1u << i) : 0u;
-        s.a[1] |= (sl == 1) ? (1u << i) : 0u;
-        s.a[2] |= (sl == 2) ? (1u << i) : 0u;
-        s.a[3] |= (sl == 3) ? (1u << i) : 0u;
-    }
-    return s;
-}
-
-// Which of the (at most 36 distinct + two constant) values mv[] each element of the N x M metadata block shows
-// (gridworld_ctf.py:1044-1067): mv[0] step fraction, mv[1 + t] capture ratio for a viewer of team t, mv[4 + j] the
-// uint8-truncated hp of agent j, mv[20 + j] has_flag[j], mv[40] = 1.0, mv[41] = 0.0.
-__device__ __forceinline__ void obs_meta_lut(const DevCfg& cfg, uint8_t* mlut, uint16_t* mv, int lane) {
-    const int N = cfg.N, M = cfg.M;
-    for (int idx = lane; idx < N * M; idx += WAVE) {
-        const int i = (int)fdiv((uint32_t)idx, cfg.div_m), k = idx - i * M;
-        const int team = cfg_team(cfg, i);
-        int src = 41;
-        if (k == 0) src = 0;
-        else if (k == 1) src = 1 + team;
-        else if (k < 6) src = (k - 2 == cfg_type(cfg, i)) ? 40 : 41;
-        else {
-            // rows 6,7: the agent itself; then own-team list minus self, then the opponents list (:1053-1067)
-            int who = i;
-            if (k >= 8) {
-                const int pidx = (k - 8) >> 1;
-                const int n_own = cfg_nopp(cfg, 1 - team), n_op = cfg_nopp(cfg, team);
-                const int self_idx = (int)((pin64(cfg.self_idx_pack) >> (4 * i)) & 15u);
-                const int n_mates = n_own - (self_idx < n_own ? 1 : 0);
-                if (pidx < n_mates) who = cfg_opp(cfg, 1 - team, pidx + (pidx >= self_idx ? 1 : 0));
-                else if (pidx - n_mates < n_op) who = cfg_opp(cfg, team, pidx - n_mates);
-                else who = -1;
-            }
-            if (who >= 0) src = ((k & 1) ? 20 : 4) + who;
-        }
-        mlut[idx] = (uint8_t)src;
-    }
-    if (lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
-}
-
-// Everything of one env except the streaming: bitmap (zero + hot bits + own-position bits) into `bits`, metadata rows
-// to global memory.  `recw` / `cells` are the lane's dword of the env's record / grid (lane-clamped loads).
-// srec / mv / mstage are the calling wave's scratch.  Ends with the wave's LDS traffic drained.
-__device__ __forceinline__ void obs_build_env(const DevCfg& cfg, const DevPtrs& p, int e, uint32_t recw, uint32_t cells,
-                                              uint8_t* srec, uint16_t* mv, uint16_t* mstage, const uint8_t* mlut, uint32_t* bits,
-                                              const ObsSlots& slots, uint32_t reverse_mask, int lane, bool obs,
-                                              uint16_t* __restrict__ meta) {
-    const int N = cfg.N, G = cfg.G, GG = cfg.GG, M = cfg.M;
-    const int BQ = obs_bitmap_bytes(cfg.obs_bytes) / 16;
-    const int GW = cfg.GS / 4;  // <= 256 dwords: up to 4 passes of 64 lanes
-    const bool has_cells = obs && !(OBS_ABLATE & 4);
-    const uint32_t* slot_agents = slots.a;
-    // ---- zero the bitmap, park the record in LDS
-    if (obs) {
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-        for (int q = lane; q < BQ; q += WAVE) ((u32x4_t*)bits)[q] = z;
-    }
-    if (lane < cfg.RS / 4) ((uint32_t*)srec)[lane] = recw;
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- hot bits of every tile plane
-    if (has_cells) {
-        for (int w = lane; w < GW; w += WAVE) {
-            if (w >= WAVE) cells = ((const uint32_t*)(p.grid + (size_t)e * cfg.GS))[w];  // G > 16 only
-            int r = (int)fdiv((uint32_t)(w * 4), cfg.div_g), c = w * 4 - r * G;
-            #pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int cell = w * 4 + b;
-                const uint32_t v = (cells >> (8 * b)) & 0xFFu;
-                if (v != 0 && cell < GG) {
-                    const int fl = flip_cell(cfg, cell, r, c);
-                    #pragma unroll
-                    for (int slot = 0; slot < 4; slot++) {
-                        if (slot_agents[slot]) {  // uniform
-                            // nibble v of the 64-bit LUT with 32-bit ops (a 64-bit variable shift is several times slower)
-                            const uint64_t lut = pin64(cfg.chan_lut[slot >> 1]);
-                            const uint32_t code = (((v & 8u) ? (uint32_t)(lut >> 32) : (uint32_t)lut) >> (4 * (v & 7u))) & 15u;
-                            if (code != CTF_TILE_NONE) {
-                                const uint32_t q = code * (uint32_t)GG + (uint32_t)((slot & 1) ? fl : cell);
-                                for (uint32_t m = slot_agents[slot]; m; m &= m - 1) {  // uniform loop over the slot's agents
-                                    const uint32_t bit = (uint32_t)(__ffs((int)m) - 1) * (uint32_t)cfg.CGG + q;
-                                    atomicOr(bits + (bit >> 5), 1u << (bit & 31u));
-                                }
-                            }
-                        }
-                    }
-                }
-                if (++c == G) { c = 0; r++; }
-            }
-        }
-    }
-    // ---- plane 0: the viewer's own position
-    if (obs && lane < N) {
-        const int8_t* ps = (const int8_t*)(srec + cfg.off_pos);
-        const int r = ps[2 * lane], c = ps[2 * lane + 1];
-        const int cell = ((reverse_mask >> lane) & 1u) ? flip_cell(cfg, r * G + c, r, c) : r * G + c;
-        const uint32_t bit = (uint32_t)lane * (uint32_t)cfg.CGG + (uint32_t)cell;
-        atomicOr(bits + (bit >> 5), 1u << (bit & 31u));
-    }
-
-    // ---- metadata (gridworld_ctf.py:1027-1069).  A: the few distinct values, as f16 bits
-    if (meta && !(OBS_ABLATE & 8)) {
-        const int32_t* misc = (const int32_t*)(srec + cfg.off_misc);
-        if (lane < 36) {
-            double val = 0.0;
-            if (lane == META_MV_STEP) val = meta_step_fraction(misc[0], cfg.game_steps);
-            else if (lane < META_MV_RATIO + 2) val = meta_capture_ratio(misc[lane], misc[3 - lane]);  // viewer team lane-1
-            else if (lane >= META_MV_HP && lane < META_MV_HP + N) val = (double)meta_hp_u8(cfg, srec, lane - META_MV_HP);
-            else if (lane >= META_MV_FLAG && lane < META_MV_FLAG + N) val = (double)srec[cfg.off_flag + lane - META_MV_FLAG];
-            mv[lane] = f64_to_f16(val);
-        }
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-        // B: every element of the N x M block is one of those values (which one: obs_meta_lut, built once per wave)
-        for (int idx = lane; idx < N * M; idx += WAVE) mstage[idx] = mv[mlut[idx]];
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-        // C: N*M*2 = 4N(N+3) bytes, always a multiple of 8
-        u32x2_t* mdst = (u32x2_t*)(meta + (size_t)e * N * M);
-        if (!(OBS_ABLATE & 16))
-        for (int q = lane; q < N * M / 4; q += WAVE) mdst[q] = ((const u32x2_t*)mstage)[q];
-    }
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);  // the bitmap's atomic ORs have landed
-    __builtin_amdgcn_wave_barrier();
-
-}
 
 // one 16-byte chunk of the observation block: h = halfword k of the bitmap, every bit expanded to a byte
 template <int ALIGN>
@@ -511,458 +330,6 @@ __global__ void __launch_bounds__(256) k_observe(DevCfg cfg, DevPtrs p, uint8_t*
         __builtin_amdgcn_s_waitcnt(LGKM_ONLY);  // this env's LDS reads are done before the next env reuses the bitmap
         __builtin_amdgcn_wave_barrier();
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// observe into a RETAINED buffer — only the 128-byte lines whose bytes changed since the last render into it
-// ------------------------------------------------------------------------------------------------
-// The caller has promised (ctf_obs_retain) that nobody but this handle writes the buffer, and the handle keeps a shadow of what it
-// last rendered there (ObsShadow, ctf_device.h).  One wave per env, one env per wave:
-//   1. all loads first: the env's record and grid, the shadow's grid and positions, the shadow's key;
-//   2. the env's bitmap and its metadata rows exactly as k_observe makes them (obs_build_env: the rows are written whole);
-//   3. the dirty lines of the env's span (ctf_obs_delta.h has the rule): XOR of the two grids names the changed cells, a moved
-//      viewer its two bytes of plane 0; a key that is not the expected one makes every line dirty — that is the first render,
-//      an invalidation and a change of the reverse mask, with no other code for any of them;
-//   4. the dirty lines' indices compacted into a list (popcount prefix over the mask dwords), then eight lines per store
-//      instruction: lanes 8k .. 8k+7 write the eight 16-byte chunks of the k-th line of the pass from the bitmap; chunks outside
-//      the env's own block belong to the neighbour's wave and are skipped (blocks are whole chunks);
-//   5. the shadow dwords that differ are written back, and the key where it was not the expected one.
-// State that changed behind the render (reset, auto-reset, set_state, import, restore) needs no notice: the shadow is compared
-// with the state itself.  Envs go to XCDs in contiguous eighths as in k_observe.
-// Per-wave LDS: [rec RS][mvals 96][meta staging][bitmap][line mask][line list u16].
-// This is the kernel of round 11, kept selectable (CTF_OBS_DELTA_BITMAP=1 at ctf_obs_retain) until k_observe_delta below has held
-// its numbers on more than one box.
-__host__ __device__ inline int delta_mask_bytes(int obs_bytes) { return ((obsd_lines(obs_bytes, CTF_OBS_LINE - 16) + 31) / 32 * 4 + 15) & ~15; }
-__host__ __device__ inline int delta_list_bytes(int obs_bytes) { return (obsd_lines(obs_bytes, CTF_OBS_LINE - 16) * 2 + 15) & ~15; }
-__host__ __device__ inline int delta_bitmap_wave_bytes(int RS, int N, int M, int obs_bytes) {
-    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + obs_bitmap_bytes(obs_bytes) + delta_mask_bytes(obs_bytes) + delta_list_bytes(obs_bytes);
-}
-#define OBS_DELTA_UNROLL 4  // store instructions (of eight lines each) per pass, their bitmap halfwords read first
-
-template <int STORE_NT>
-__global__ void __launch_bounds__(256) k_observe_delta_bitmap(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
-                                                                     uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map) {
-    extern __shared__ uint32_t lds[];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4;
-    const uint32_t b = blockIdx.x;
-    const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
-    const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
-    if (e >= cfg.n_envs) return;  // (the whole wave: nothing below synchronises across waves)
-    uint8_t* wl = (uint8_t*)lds + wave * delta_bitmap_wave_bytes(cfg.RS, N, M, OB);
-    uint8_t* srec = wl;
-    uint16_t* mv = (uint16_t*)(wl + cfg.RS);
-    uint16_t* mstage = (uint16_t*)(wl + cfg.RS + OBS_MV_BYTES);
-    uint32_t* bits = (uint32_t*)(wl + cfg.RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M));
-    uint32_t* lmask = (uint32_t*)((uint8_t*)bits + obs_bitmap_bytes(OB));
-    uint16_t* llist = (uint16_t*)((uint8_t*)lmask + delta_mask_bytes(OB));
-
-    // ---- 1. loads, all issued before anything waits, on clamped indices
-    const uint32_t* gcur = (const uint32_t*)(p.grid + (size_t)e * cfg.GS);
-    uint32_t* gsh = (uint32_t*)(sh.grid + (size_t)e * cfg.GS);
-    const uint32_t recw = ((const uint32_t*)(p.rec + (size_t)e * cfg.RS))[min(lane, cfg.RS / 4 - 1)];
-    uint32_t cur[4], old[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {  // G <= 32: at most 256 grid dwords (uniform conditions)
-        cur[j] = (GW > WAVE * j) ? gcur[min(lane + WAVE * j, GW - 1)] : 0u;
-        old[j] = (GW > WAVE * j) ? gsh[min(lane + WAVE * j, GW - 1)] : 0u;
-    }
-    uint16_t* psh = sh.pos + (size_t)e * CTF_MAX_AGENTS;
-    const uint32_t old_pos = psh[min(lane, N - 1)];
-    const uint32_t key = CTF_OBS_KEY(reverse_mask);
-    const bool known = sh.key[e] == key;  // uniform
-
-    // ---- 2. bitmap + metadata rows
-    if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
-    const ObsSlots slots = obs_slots(cfg, reverse_mask);
-    obs_build_env(cfg, p, e, recw, cur[0], srec, mv, mstage, p.meta_lut, bits, slots, reverse_mask, lane, true, meta);
-
-    // ---- 3. the dirty lines of the env's span
-    const size_t base = (size_t)e * (size_t)OB;
-    const int lead = (int)(((uintptr_t)obs + base) & (uintptr_t)(CTF_OBS_LINE - 1));  // a multiple of 16
-    const int nl = obsd_lines(OB, lead), ndw = (nl + 31) >> 5;                       // ndw <= 64 (obsd_applies)
-    if (lane < ndw) {
-        const int left = nl - 32 * lane;
-        lmask[lane] = known ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
-    }
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t cur_pos = *(const uint16_t*)(srec + cfg.off_pos + 2 * min(lane, N - 1));
-    if (known) {
-        ObsDeltaShape s;
-        s.N = N; s.G = cfg.G; s.GG = cfg.GG; s.CGG = cfg.CGG; s.obs_bytes = OB; s.flip_axis = cfg.flip_axis;
-        s.team_mask = cfg.team_mask; s.chan_lut[0] = cfg.chan_lut[0]; s.chan_lut[1] = cfg.chan_lut[1];
-        auto mark = [&](int line) {
-            if ((uint32_t)line < (uint32_t)nl) atomicOr(lmask + (line >> 5), 1u << (line & 31));
-        };
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int w = lane + WAVE * j;
-            const uint32_t x = cur[j] ^ old[j];
-            if (GW > WAVE * j && w < GW && x) {
-                for (int q = 0; q < 4; q++) {
-                    const int cell = 4 * w + q;
-                    if (((x >> (8 * q)) & 0xFFu) && cell < cfg.GG)
-                        obsd_cell_changed(s, reverse_mask, lead, cell, (old[j] >> (8 * q)) & 0xFFu, (cur[j] >> (8 * q)) & 0xFFu, mark);
-                }
-            }
-        }
-        if (lane < N && cur_pos != old_pos) {
-            const int oc = (int)(int8_t)(old_pos & 0xFFu) * cfg.G + (int)(int8_t)(old_pos >> 8);
-            const int nc = (int)(int8_t)(cur_pos & 0xFFu) * cfg.G + (int)(int8_t)(cur_pos >> 8);
-            obsd_viewer_moved(s, reverse_mask, lead, lane, oc, nc, mark);
-        }
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-    }
-
-    // ---- 4. compact: lane q lists the set bits of mask dword q behind those of the dwords before it
-    uint32_t m = lane < ndw ? lmask[lane] : 0u;
-    int incl = __popc(m);
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int up = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += up;
-    }
-    const int total = __shfl(incl, WAVE - 1, WAVE);
-    for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-    __builtin_amdgcn_wave_barrier();
-    // ... and emit: lanes 8k .. 8k+7 hold the eight chunks of one line
-    {
-        uint8_t* out = obs + base;
-        const uint16_t* hb = (const uint16_t*)bits;
-        const int sub = lane >> 3, off_in_line = (lane & 7) * 16 - lead;
-        for (int l0 = 0; l0 < total; l0 += 8 * OBS_DELTA_UNROLL) {
-            uint32_t h[OBS_DELTA_UNROLL];
-            int k[OBS_DELTA_UNROLL];
-#pragma unroll
-            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
-                const int idx = l0 + 8 * u + sub;
-                const int o = idx < total ? (int)llist[idx] * CTF_OBS_LINE + off_in_line : -1;  // byte of the env's block
-                k[u] = (o >= 0 && o < OB) ? o >> 4 : -1;
-                h[u] = k[u] >= 0 ? hb[k[u]] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
-                if (k[u] >= 0) {
-                    const u32x4_t v = {expand4(h[u], 0), expand4(h[u], 1), expand4(h[u], 2), expand4(h[u], 3)};
-                    if (STORE_NT) __builtin_nontemporal_store(v, (u32x4_t*)(out + ((size_t)k[u] << 4)));
-                    else *(u32x4_t*)(out + ((size_t)k[u] << 4)) = v;
-                }
-            }
-        }
-    }
-
-    // ---- 5. the shadow follows what the buffer now holds
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int w = lane + WAVE * j;
-        if (GW > WAVE * j && w < GW && (!known || cur[j] != old[j])) gsh[w] = cur[j];
-    }
-    if (lane < N && (!known || cur_pos != old_pos)) psh[lane] = (uint16_t)cur_pos;
-    if (!known && lane == 0) sh.key[e] = key;
-}
-// The same render without the block's bitmap (round 12; ctf_obs_chunk.h has the chunk rule).  The round-11 kernel is bound by the
-// vector ALU, not by a chain of latencies: while its waves are resident the SIMD's VALU is busy all the time (1 220 vector
-// instructions per wave, profiles/r12_delta_direct.md).  So this one issues fewer of them:
-//   - instead of one LDS OR per non-empty cell and VIEWING AGENT into N * CGG bits, one per cell and SLOT in use (viewer team x
-//     reversed: two for the default mask) into the slots' images of CGG bits each; a lane then takes its chunk's 16 bits from its
-//     view's slot image at bit (offset % CGG), ORs in the viewer's own cell and expands them (obsc_chunk_bits) — a first render
-//     (unknown key) goes the same way, every line being dirty;
-//   - the changed cells are first gathered into a list (ballot + lane count) and then marked one cell per lane, instead of every
-//     lane walking the four bytes of its dword in turn with the whole wave waiting on each;
-//   - the viewers' positions come from global memory with the other loads, so nothing waits for the record in LDS before the
-//     stores; the metadata rows (which need it) are made after the dirty lines' stores have been issued.
-// LDS operations of a wave complete in order, so the zeroing, the ORs and the mask's initialisation need no wait between them.
-// Round 13 takes out work the result does not need (profiles/r13_delta_images.md):
-//   - the slot images are a pure function of the grid the shadow already holds, so the shadow keeps them (ObsShadow.images) and a
-//     render with a known key loads them with its other loads, parks them in LDS and moves one bit per changed cell and slot
-//     (obsc_update_slot, a lane per (changed cell, slot)); the same lanes write the touched dwords back once the LDS operations
-//     have completed.  Two passes may touch one dword: the later pass's store carries the later value and a wave's stores to one
-//     address land in the order they were issued.  An unknown key (first render, invalidation, mask change) builds the images
-//     from all cells as before and writes the slots in use to the shadow whole.  REBUILD (CTF_OBS_DELTA_REBUILD=1) is round 12's
-//     behaviour: built at every render, the shadow's images neither read nor written;
-//   - the dirty lines are marked by one lane per (changed cell, viewer) pair (obsd_pair_changed_at) instead of one lane per cell
-//     walking teams and viewers in a scalar loop on a nearly empty wave: 0.015 of the 0.020 ms the round takes off step + render
-//     (0.177 -> 0.156 ms; the carried images give 0.002).
-// (Compacting the mask 64 lines per pass with the mask's dwords as ballots, in place of the scan and the per-lane bit loop of
-// step 4, was built and measured too: it lost 0.005 ms and is not here.)
-// Round 17 (profiles/r17_delta_append.md): a moved viewer's two bytes come from the row and column bytes of both positions
-// (obsd_viewer_moved_rc: two divisions less per wave), every small product of the known-key path is a 24-bit multiply (OBSD_MUL:
-// 178 -> 10 quarter-rate integer multiplies in the kernel's text, the fdivs remain), and a lane works out where its image unit
-// lies once.  590 vector instructions per wave where there were 640, the same bytes.  The dirty-line list made by APPEND instead
-// of step 4's scan — a mark as an LDS atomicOr that returns the old dword, the lane that finds its bit clear taking a place with
-// an atomicAdd — was priced first (step 4 replaced by an identity list: 0.0037 ms, under the bar), built all the same, passed
-// every test and was 0.008 ms SLOWER in every round: two dependent LDS round trips per mark where the scan has none.  Not here.
-// `all_dirty` (CTF_OBS_DELTA_ALL_DIRTY=1, tests and soaks): every line is rewritten although the key is known, the images still
-// carried forward — every byte of the buffer then shows what the retained images hold.
-// Per-wave LDS: [rec RS][mvals 96][meta staging][slot images 4 x][own cells u16[16]][changed cells u32[GS]][line mask][line list u16].
-__host__ __device__ inline int delta_wave_bytes(int RS, int N, int M, int CGG, int GS, int obs_bytes) {
-    return RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M) + 16 * obsc_image_dwords(CGG) + 2 * CTF_MAX_AGENTS + 4 * GS + delta_mask_bytes(obs_bytes) +
-           delta_list_bytes(obs_bytes);
-}
-
-#ifndef OBS_DELTA_META_FIRST
-#define OBS_DELTA_META_FIRST 0  // 1 = profiling comparison only: the metadata rows made before the dirty lines are marked and stored
-#endif
-
-#define OBS_DELTA_IMG_REGS 2  // 16-byte units of the shadow's images a lane loads with the first loads (the arena needs one)
-
-// META = false: the caller has the rows from elsewhere (ctf_step_observe: k_step wrote them, ctf_meta.h) — no record load, no
-// record parking and no obs_build_env in the kernel at all; `meta` is then not looked at.
-template <int STORE_NT, bool REBUILD, bool META>
-__global__ void __launch_bounds__(256) k_observe_delta(DevCfg cfg, DevPtrs p, ObsShadow sh, uint8_t* __restrict__ obs,
-                                                       uint16_t* __restrict__ meta, uint32_t reverse_mask, uint32_t xcd_map, uint32_t all_dirty) {
-    extern __shared__ uint32_t lds[];
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-    const int N = cfg.N, M = cfg.M, OB = cfg.obs_bytes, GW = cfg.GS / 4, IW = obsc_image_dwords(cfg.CGG), IU = IW / 4;
-    const uint32_t b = blockIdx.x;
-    const uint32_t lb = xcd_map ? (b & 7u) * (gridDim.x >> 3) + (b >> 3) : b;
-    const int e = (int)lb * (int)(blockDim.x / WAVE) + wave;
-    if (e >= cfg.n_envs) return;  // (the whole wave: nothing below synchronises across waves)
-    uint8_t* wl = (uint8_t*)lds + wave * delta_wave_bytes(cfg.RS, N, M, cfg.CGG, cfg.GS, OB);
-    uint8_t* srec = wl;
-    uint16_t* mv = (uint16_t*)(wl + cfg.RS);
-    uint16_t* mstage = (uint16_t*)(wl + cfg.RS + OBS_MV_BYTES);
-    uint32_t* images = (uint32_t*)(wl + cfg.RS + OBS_MV_BYTES + obs_meta_stage_bytes(N, M));
-    uint16_t* selfc = (uint16_t*)(images + 4 * IW);
-    uint32_t* chg = (uint32_t*)(selfc + CTF_MAX_AGENTS);
-    uint32_t* lmask = chg + cfg.GS;
-    uint16_t* llist = (uint16_t*)((uint8_t*)lmask + delta_mask_bytes(OB));
-
-    // ---- 1. loads, all issued before anything waits, on clamped indices
-    const uint32_t* gcur = (const uint32_t*)(p.grid + (size_t)e * cfg.GS);
-    uint32_t* gsh = (uint32_t*)(sh.grid + (size_t)e * cfg.GS);
-    const uint8_t* rec = p.rec + (size_t)e * cfg.RS;
-    uint32_t recw = 0u;
-    if constexpr (META) recw = ((const uint32_t*)rec)[min(lane, cfg.RS / 4 - 1)];
-    const uint32_t cur_pos = *(const uint16_t*)(rec + cfg.off_pos + 2 * min(lane, N - 1));
-    uint32_t cur[4], old[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {  // G <= 32: at most 256 grid dwords (uniform conditions)
-        cur[j] = (GW > WAVE * j) ? gcur[min(lane + WAVE * j, GW - 1)] : 0u;
-        old[j] = (GW > WAVE * j) ? gsh[min(lane + WAVE * j, GW - 1)] : 0u;
-    }
-    uint16_t* psh = sh.pos + (size_t)e * CTF_MAX_AGENTS;
-    const uint32_t old_pos = psh[min(lane, N - 1)];
-    const uint32_t key = CTF_OBS_KEY(reverse_mask);
-    const bool known = sh.key[e] == key;  // uniform
-
-    ObsDeltaShape s;
-    s.N = N; s.G = cfg.G; s.GG = cfg.GG; s.CGG = cfg.CGG; s.obs_bytes = OB; s.flip_axis = cfg.flip_axis;
-    s.team_mask = cfg.team_mask; s.chan_lut[0] = cfg.chan_lut[0]; s.chan_lut[1] = cfg.chan_lut[1];
-    const uint32_t used = obsc_slots_used(s, reverse_mask);
-    const size_t base = (size_t)e * (size_t)OB;
-    const int lead = (int)(((uintptr_t)obs + base) & (uintptr_t)(CTF_OBS_LINE - 1));  // a multiple of 16
-    const int nl = obsd_lines(OB, lead), ndw = (nl + 31) >> 5;                       // ndw <= 64 (obsd_applies)
-    // the shadow's images of the slots in use, 16 bytes per lane: unit q of [rank of the slot among those in use][IU] is unit
-    // slot * IU + u of the env's [4][IU]
-    uint32_t* ish = sh.images + (size_t)e * (size_t)(4 * IW);
-    uint32_t slot_of_rank = 0u;  // nibble k = the k-th slot in use
-    int n_iu = 0;
-    for (int sl = 0; sl < 4; sl++)
-        if (used & (1u << sl)) { slot_of_rank |= (uint32_t)sl << (4 * n_iu); n_iu++; }
-    n_iu *= IU;
-    auto image_unit = [&](int q) {
-        const int k = (q >= IU) + (q >= 2 * IU) + (q >= 3 * IU);
-        return q + OBSD_MUL((int)((slot_of_rank >> (4 * k)) & 3u) - k, IU);
-    };
-    u32x4_t img[OBS_DELTA_IMG_REGS];
-    int img_at[OBS_DELTA_IMG_REGS];  // where the unit lies in the env's [4][IU], shadow and LDS alike: worked out once
-    if (!REBUILD) {
-#pragma unroll
-        for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
-            if (n_iu > WAVE * j) {  // (uniform condition)
-                img_at[j] = image_unit(min(lane + WAVE * j, n_iu - 1));
-                img[j] = ((const u32x4_t*)ish)[img_at[j]];
-            }
-    }
-    const bool build = REBUILD || !known;  // uniform
-
-    // ---- 2. everything the loaded registers give, into LDS: the slot images, the viewers' own cells, the mask's start, the
-    // list of changed cells
-    if (build) {
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-        for (int q = lane; q < IW; q += WAVE) ((u32x4_t*)images)[q] = z;  // 4 images of IW dwords = IW x 16 bytes
-    } else if (!REBUILD) {
-#pragma unroll
-        for (int j = 0; j < OBS_DELTA_IMG_REGS; j++)
-            if (lane + WAVE * j < n_iu) ((u32x4_t*)images)[img_at[j]] = img[j];  // (not clamped for such a lane)
-        for (int q = lane + WAVE * OBS_DELTA_IMG_REGS; q < n_iu; q += WAVE)  // larger shapes: the rest, loaded here
-            ((u32x4_t*)images)[image_unit(q)] = ((const u32x4_t*)ish)[image_unit(q)];
-    }
-    if constexpr (META)
-        if (meta && lane == 0) { mv[40] = 0x3C00u; mv[41] = 0u; }
-    if (lane < ndw) {
-        const int left = nl - 32 * lane;
-        lmask[lane] = (known && !all_dirty) ? 0u : (left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u);
-    }
-    if (lane < N) selfc[lane] = (uint16_t)obsc_self_cell(s, reverse_mask, lane, (int)(int8_t)(cur_pos & 0xFFu), (int)(int8_t)(cur_pos >> 8));
-    if (build) {  // from all cells
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int w = lane + WAVE * j;
-            if (GW > WAVE * j) {  // uniform
-                const bool mine = w < GW;
-                int r = (int)fdiv((uint32_t)(mine ? w * 4 : 0), cfg.div_g), c = (mine ? w * 4 : 0) - OBSD_MUL(r, cfg.G);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int cell = 4 * w + q;
-                    if (mine && cell < cfg.GG)
-                        obsc_build_cell(s, used, cell, r, c, (cur[j] >> (8 * q)) & 0xFFu,
-                                        [&](int slot, int bit) { atomicOr(images + OBSD_MUL(slot, IW) + (bit >> 5), 1u << (bit & 31)); });
-                    if (++c == cfg.G) { c = 0; r++; }
-                }
-            }
-        }
-    }
-    int n_chg = 0;  // uniform
-    if (known) {    // the changed cells, gathered: cell | old tile << 16 | new tile << 24
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int w = lane + WAVE * j;
-            const uint32_t x = cur[j] ^ old[j];
-            if (GW > WAVE * j && __ballot(w < GW && x != 0u)) {  // uniform
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int cell = 4 * w + q;
-                    const bool ch = w < GW && cell < cfg.GG && ((x >> (8 * q)) & 0xFFu) != 0u;
-                    const uint64_t bal = __ballot(ch);
-                    if (bal) {  // uniform
-                        if (ch) chg[n_chg + obsd_rank(bal, lane)] = (uint32_t)cell | (((old[j] >> (8 * q)) & 0xFFu) << 16) | (((cur[j] >> (8 * q)) & 0xFFu) << 24);
-                        n_chg += __popcll(bal);
-                    }
-                }
-            }
-        }
-    }
-
-    const ObsSlots no_slots = {{0, 0, 0, 0}};
-    if constexpr (META && OBS_DELTA_META_FIRST)
-        if (meta)
-            obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
-
-    // ---- 3. the dirty lines of the env's span: one changed cell per lane, then the viewers that moved
-    if (known) {
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-        auto mark = [&](int line) {
-            if ((uint32_t)line < (uint32_t)nl) atomicOr(lmask + (line >> 5), 1u << (line & 31));
-        };
-        // a lane per (changed cell, viewer): viewers padded to a power of two, so a pair's cell and viewer are a shift and a mask
-        const int vsh = N > 1 ? 32 - __clz(N - 1) : 0, n_pairs = n_chg << vsh;
-        for (int at = 0; at < n_pairs; at += WAVE) {
-            const int ci = (at + lane) >> vsh, i = (at + lane) & ((1 << vsh) - 1);
-            if (ci < n_chg && i < N) {
-                const uint32_t ent = chg[ci];
-                const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
-                obsd_pair_changed_at(s, lead, ((reverse_mask >> i) & 1u) ? obsc_flip_rc(s, cell, r, cell - OBSD_MUL(r, cfg.G)) : cell, i,
-                                     (ent >> 16) & 0xFFu, ent >> 24, mark);
-            }
-        }
-        if (lane < N && cur_pos != old_pos)  // from the row and column bytes of both positions: no division (round 17)
-            obsd_viewer_moved_rc(s, reverse_mask, lead, lane, (int)(int8_t)(old_pos & 0xFFu), (int)(int8_t)(old_pos >> 8), (int)(int8_t)(cur_pos & 0xFFu),
-                                 (int)(int8_t)(cur_pos >> 8), mark);
-        if (!REBUILD) {
-            // the images follow the grid: a lane per (changed cell, slot) moves its bit, then stores the dwords it touched
-            for (int at = 0; at < 4 * n_chg; at += WAVE) {
-                const int ci = (at + lane) >> 2, slot = (at + lane) & 3;
-                int w_clear = -1, w_set = -1;
-                if (ci < n_chg && (used & (1u << slot))) {
-                    const uint32_t ent = chg[ci];
-                    const int cell = (int)(ent & 0xFFFFu), r = (int)fdiv((uint32_t)cell, cfg.div_g);
-                    obsc_update_slot(s, slot, cell, r, cell - OBSD_MUL(r, cfg.G), (ent >> 16) & 0xFFu, ent >> 24,
-                                     [&](int sl, int bit) { w_clear = OBSD_MUL(sl, IW) + (bit >> 5); atomicAnd(images + w_clear, ~(1u << (bit & 31))); },
-                                     [&](int sl, int bit) { w_set = OBSD_MUL(sl, IW) + (bit >> 5); atomicOr(images + w_set, 1u << (bit & 31)); });
-                }
-                __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-                __builtin_amdgcn_wave_barrier();
-                if (w_clear >= 0) ish[w_clear] = images[w_clear];
-                if (w_set >= 0) ish[w_set] = images[w_set];
-            }
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-    __builtin_amdgcn_wave_barrier();
-
-    // ---- 4. compact: lane q lists the set bits of mask dword q behind those of the dwords before it
-    uint32_t m = lane < ndw ? lmask[lane] : 0u;
-    int total;
-    if (OBS_ABLATE & 32) {  // profiling only, the price of the compaction (profiles/r17_delta_append.md): as many lines, the wrong ones
-        uint32_t* cnt = (uint32_t*)llist;
-        if (lane == 0) *cnt = 0u;
-        if (m) atomicAdd(cnt, (uint32_t)__popc(m));
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-        total = __builtin_amdgcn_readfirstlane((int)*cnt);
-        __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-        __builtin_amdgcn_wave_barrier();
-        for (int q = lane; q < total; q += WAVE) llist[q] = (uint16_t)q;
-    } else {
-        int incl = __popc(m);
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const int up = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += up;
-        }
-        total = __shfl(incl, WAVE - 1, WAVE);
-        for (int at = incl - __popc(m); m; m &= m - 1u) llist[at++] = (uint16_t)(32 * lane + __ffs((int)m) - 1);
-    }
-    __builtin_amdgcn_s_waitcnt(LGKM_ONLY);
-    __builtin_amdgcn_wave_barrier();
-    // ... and emit: lanes 8k .. 8k+7 hold the eight chunks of one line; chunks outside the env's own block belong to the
-    // neighbour's wave and are skipped (blocks are whole chunks)
-    {
-        uint8_t* out = obs + base;
-        const int sub = lane >> 3, off_in_line = (lane & 7) * 16 - lead;
-        for (int l0 = 0; l0 < total; l0 += 8 * OBS_DELTA_UNROLL) {
-            uint32_t h[OBS_DELTA_UNROLL];
-            int o[OBS_DELTA_UNROLL];
-#pragma unroll
-            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
-                const int idx = l0 + 8 * u + sub;
-                o[u] = idx < total ? (int)llist[idx] * CTF_OBS_LINE + off_in_line : -1;  // byte of the env's block
-                if (o[u] >= OB) o[u] = -1;
-                h[u] = 0u;
-                if (o[u] >= 0) {
-                    const int view = (int)fdiv((uint32_t)o[u], cfg.div_cgg);
-                    h[u] = obsc_chunk_bits(s, reverse_mask, images, IW, selfc, view, o[u] - OBSD_MUL(view, cfg.CGG));
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < OBS_DELTA_UNROLL; u++) {
-                if (o[u] >= 0) {
-                    const u32x4_t v = {obsc_expand4(h[u], 0), obsc_expand4(h[u], 1), obsc_expand4(h[u], 2), obsc_expand4(h[u], 3)};
-                    if (STORE_NT) __builtin_nontemporal_store(v, (u32x4_t*)(out + o[u]));
-                    else *(u32x4_t*)(out + o[u]) = v;
-                }
-            }
-        }
-    }
-
-    // ---- 5. the metadata rows, whole (obs_build_env parks the record in LDS and makes them from it)
-    if constexpr (META && !OBS_DELTA_META_FIRST)
-        if (meta)
-            obs_build_env(cfg, p, e, recw, 0u, srec, mv, mstage, p.meta_lut, nullptr, no_slots, reverse_mask, lane, false, meta);
-
-    // ---- 6. the shadow follows what the buffer now holds
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int w = lane + WAVE * j;
-        if (GW > WAVE * j && w < GW && (!known || cur[j] != old[j])) gsh[w] = cur[j];
-    }
-    if (lane < N && (!known || cur_pos != old_pos)) psh[lane] = (uint16_t)cur_pos;
-    if (!REBUILD && !known)  // the images built from all cells: the slots in use, whole
-        for (int q = lane; q < n_iu; q += WAVE) ((u32x4_t*)ish)[image_unit(q)] = ((const u32x4_t*)images)[image_unit(q)];
-    if (!known && lane == 0) sh.key[e] = key;
-}
-// Everything about the retained buffer is unknown again (ctf_obs_invalidate; behind every other launch that writes the buffer)
-extern "C" __global__ void k_obs_key_clear(uint32_t* key, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) key[i] = 0u;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1398,22 +765,10 @@ extern "C" __global__ void k_random_actions(DevCfg cfg, int8_t* actions, uint64_
 // ------------------------------------------------------------------------------------------------
 // launchers (ctf_launch.h; called from ctf_abi.hip)
 // ------------------------------------------------------------------------------------------------
-// ---- integer knobs of the environment (tests, profiling).  Read at every call unless said otherwise: tests flip them inside
-// one process.
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static bool obs_xcd_knob() { return env_int("CTF_OBS_XCD", 1) != 0; }  // 0: launch-order tiles / plain grid-stride envs (profiling); default: XCD-contiguous
+// (env_int, obs_xcd_knob, obs_waves_per_block — the knobs the retained render's launcher reads too: ctf_render_dev.h)
 static int obs_reserve_blocks() {  // read once
     static const int v = env_int("CTF_OBS_RESERVE_BLOCKS", 0);
     return v < 0 ? 0 : v;
-}
-// waves per block of the wave-per-env renders: 4 unless one env's LDS is so large that 4 of them would crowd the CU's LDS
-static int obs_waves_per_block(int per_wave) {
-    int wpb = 4;
-    while (wpb > 1 && wpb * per_wave > 40 * 1024) wpb >>= 1;
-    return wpb;
 }
 // (with_bool / with_step_variant, run-time switches -> template arguments: ctf_step_block.h)
 
@@ -1547,39 +902,6 @@ extern "C" hipError_t ctf_launch_observe(const DevCfg& cfg, const DevPtrs& p, co
     if (align == 16) hipLaunchKernelGGL(k_observe<16>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
     else if (align == 4) hipLaunchKernelGGL(k_observe<4>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
     else hipLaunchKernelGGL(k_observe<1>, grid, block, sh, st, cfg, p, r.obs, r.meta, r.reverse_mask, xcd_map);
-    return hipGetLastError();
-}
-// the one rule by which a render into a retained `obs` can be the delta render: whole 16-byte chunks at 16-byte aligned addresses
-// and a span of lines the kernel's mask holds (ctf_obs_delta.h)
-extern "C" int ctf_observe_delta_applies(const DevCfg& cfg, const uint8_t* obs) {
-    return obs && ((uintptr_t)obs % 16) == 0 && obsd_applies(cfg.obs_bytes);
-}
-// k_observe_delta: one wave per env, up to 4 independent waves per block, a multiple of 8 blocks (XCD-contiguous envs);
-// bitmap != 0: the round-11 kernel (CTF_OBS_DELTA_BITMAP=1)
-extern "C" hipError_t ctf_launch_observe_delta(const DevCfg& cfg, const DevPtrs& p, const ObsShadow& shadow, const RenderArgs& r, int store_nt,
-                                               int bitmap, uint32_t flags, hipStream_t st) {
-    const int per_wave = bitmap ? delta_bitmap_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.obs_bytes)
-                                : delta_wave_bytes(cfg.RS, cfg.N, cfg.M, cfg.CGG, cfg.GS, cfg.obs_bytes);
-    const int wpb = obs_waves_per_block(per_wave);
-    const size_t sh = (size_t)wpb * per_wave;
-    const unsigned blocks = (unsigned)(((cfg.n_envs + wpb - 1) / wpb + 7) / 8 * 8);
-    const uint32_t xcd_map = obs_xcd_knob();
-    with_bool(store_nt != 0, [&](auto NT) {
-        if (bitmap)
-            hipLaunchKernelGGL(k_observe_delta_bitmap<NT.value>, dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs, r.meta,
-                               r.reverse_mask, xcd_map);
-        else
-            with_bool((flags & CTF_OBS_DELTA_F_REBUILD) != 0u, [&](auto RB) {
-                with_bool(r.meta != nullptr, [&](auto META) {  // no rows asked for: the instantiation without any of their code
-                    hipLaunchKernelGGL((k_observe_delta<NT.value, RB.value, META.value>), dim3(blocks), dim3(wpb * WAVE), sh, st, cfg, p, shadow, r.obs,
-                                       r.meta, r.reverse_mask, xcd_map, (flags & CTF_OBS_DELTA_F_ALL_DIRTY) ? 1u : 0u);
-                });
-            });
-    });
-    return hipGetLastError();
-}
-extern "C" hipError_t ctf_launch_obs_key_clear(const ObsShadow& shadow, int n_envs, hipStream_t st) {
-    hipLaunchKernelGGL(k_obs_key_clear, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, st, shadow.key, n_envs);
     return hipGetLastError();
 }
 extern "C" hipError_t ctf_launch_observe_codes(const DevCfg& cfg, const DevPtrs& p, uint8_t* codes, uint16_t* meta, uint16_t* selfcells,

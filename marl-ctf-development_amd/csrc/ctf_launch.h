@@ -1,5 +1,5 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip and ctf_scripted_roles.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_observe_delta.hip, ctf_step_direct.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip and ctf_scripted_roles.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,12 +43,13 @@ hipError_t ctf_launch_observe_codes(const DevCfg&, const DevPtrs&, uint8_t* code
                                     int n_cus, hipStream_t);
 hipError_t ctf_launch_export_counters(const DevCfg&, const DevPtrs&, int32_t* metrics, int32_t* captures, int32_t* steps, hipStream_t);
 hipError_t ctf_launch_random_actions(const DevCfg&, int8_t* actions, uint64_t seed, uint32_t step, uint32_t env_offset, hipStream_t);
-hipError_t ctf_launch_observe_delta(const DevCfg&, const DevPtrs&, const ObsShadow&, const RenderArgs&, int store_nt, int bitmap, uint32_t flags, hipStream_t);
-hipError_t ctf_launch_obs_key_clear(const ObsShadow&, int n_envs, hipStream_t);
-int ctf_observe_delta_applies(const DevCfg&, const uint8_t* obs);    // 1: a retained `obs` can take k_observe_delta
 int ctf_step_blocks(const DevCfg&);                                // step blocks of a step launch
 int ctf_observe_uses_tiles(const DevCfg&, const uint8_t* obs);       // 1: a render into `obs` is k_observe_tiles, 0: k_observe
 int ctf_step_observe_one_launch(const DevCfg&, const uint8_t* obs);  // 1: ctf_step_observe is k_step_observe, 0: two launches
+// ---- ctf_observe_delta.hip: the retained render
+hipError_t ctf_launch_observe_delta(const DevCfg&, const DevPtrs&, const ObsShadow&, const RenderArgs&, int store_nt, int bitmap, uint32_t flags, hipStream_t);
+hipError_t ctf_launch_obs_key_clear(const ObsShadow&, int n_envs, hipStream_t);
+int ctf_observe_delta_applies(const DevCfg&, const uint8_t* obs);    // 1: a retained `obs` can take k_observe_delta
 // ---- ctf_rng.hip (envs [e0, e0 + count): record b of the arrays belongs to env e0 + b)
 hipError_t ctf_launch_seed(const DevCfg&, const DevPtrs&, const uint64_t* py_seeds, const uint64_t* np_seeds, hipStream_t);
 hipError_t ctf_launch_import_rng(const DevCfg&, const DevPtrs&, const uint32_t* py, const uint32_t* np_, int e0, int count, hipStream_t);

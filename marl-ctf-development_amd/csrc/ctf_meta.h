@@ -9,13 +9,13 @@
 //                           whose INDEX is type(j), over the full hp of type(j)
 //   mv[META_MV_FLAG + j]    has_flag[j]
 //   mv[META_MV_ONE / ZERO]  1.0 and 0.0 (the one-hot type columns, the padding)
-// The renders make them one env per wave (obs_build_env, ctf_kernels.hip: a value per lane, then f64_to_f16).  The step kernels
+// The renders make them one env per wave (obs_build_env, ctf_render_dev.h: a value per lane, then f64_to_f16).  The step kernels
 // make them for all the envs of a wave at once (step_block, ctf_step_block.h), from the final records they hold in LDS:
 // meta_park_fracs and meta_park_agents lay the (env, value) pairs flat over the lanes and park each env's mv[] in its slot,
 // meta_gather_store then writes the wave's rows as flat 8-byte chunks.  The small integers (hp quotients, flags) take the exact
 // meta_u8_to_f16 there instead of the general conversion.
 //
-// Compiled for the device by ctf_kernels.hip / ctf_step_direct.hip and, with CTF_HOSTSIM defined, for the host by
+// Compiled for the device by ctf_kernels.hip / ctf_observe_delta.hip / ctf_step_direct.hip and, with CTF_HOSTSIM defined, for the host by
 // tests/hostsim/meta_main.cpp, which holds both ways to the oracle's metadata without a GPU.
 #pragma once
 #include "ctf_step_core.h"
@@ -53,8 +53,10 @@ CTF_DEV uint16_t f64_to_f16(double d) {
 }
 // the same for an integer 0 <= v < 256: eight significant bits at most, so the conversion is exact and needs no rounding
 CTF_DEV uint16_t meta_u8_to_f16(uint32_t v) {
-    const int e = 31 - ctf_clz(v | 1u);  // floor(log2 v); (v | 1: defined at 0, whose result the select below replaces)
-    const uint32_t h = ((uint32_t)(e + 15) << 10) | ((v << (10 - e)) & 0x3FFu);
+    // with e = floor(log2 v) = 31 - lz: exponent e + 15, the leading one shifted to bit 10 (by 10 - e) and masked off — written in
+    // lz itself, so that the instructions do not depend on how the compiler happens to fold the two subtractions
+    const int lz = ctf_clz(v | 1u);  // 24 .. 31; (v | 1: defined at 0, whose result the select below replaces)
+    const uint32_t h = ((uint32_t)(46 - lz) << 10) | ((v << (lz - 21)) & 0x3FFu);
     return (uint16_t)(v ? h : 0u);
 }
 

@@ -1,4 +1,4 @@
-// ctf_obs_chunk.h — the chunk rule of the retained observation render (k_observe_delta, ctf_kernels.hip): the 16 bytes of chunk k
+// ctf_obs_chunk.h — the chunk rule of the retained observation render (k_observe_delta, ctf_observe_delta.hip): the 16 bytes of chunk k
 // of an env's observation block u8 [N][C][G][G], without a bitmap of the whole block in between.
 //
 // Byte o of the block belongs to view i = o / CGG, plane c = (o % CGG) / GG and destination cell d = o % GG.  It is 1 iff
@@ -16,7 +16,7 @@
 // The images depend on the grid alone, so the handle's shadow keeps them between renders (ObsShadow.images, ctf_device.h) and a
 // render moves one bit per changed cell and slot (obsc_update_slot) instead of building them again.
 //
-// Compiled for the device by ctf_kernels.hip and for the host by tests/obs_chunk/ (checked against the oracle's renders without a
+// Compiled for the device by ctf_observe_delta.hip and for the host by tests/obs_chunk/ (checked against the oracle's renders without a
 // GPU), in the manner of ctf_obs_delta.h.  The host's obsc_chunk is the rule spelled out byte by byte; obsc_chunk_images goes through
 // the very functions the kernel calls (obsc_build_cell, obsc_self_cell, obsc_chunk_bits, obsc_expand4).
 #pragma once

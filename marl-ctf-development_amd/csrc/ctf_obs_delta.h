@@ -1,4 +1,4 @@
-// ctf_obs_delta.h — the dirty-line rule of the retained observation render (k_observe_delta, ctf_kernels.hip).
+// ctf_obs_delta.h — the dirty-line rule of the retained observation render (k_observe_delta, ctf_observe_delta.hip).
 //
 // An env's observation block u8 [N][C][G][G] is a pure function of its grid, every viewer's own position, the config and the
 // reverse mask (gridworld_ctf.py:975-1009).  When a buffer still holds the render of an OLDER state of the env (the handle's
@@ -14,7 +14,7 @@
 // lead = (address of the block's first byte) % 128.  A line shared with a neighbouring env is dirty for each env separately and
 // each env rewrites only its own bytes of it.
 //
-// Compiled for the device by ctf_kernels.hip and for the host by tests/obs_delta/ (checked against the oracle's consecutive
+// Compiled for the device by ctf_observe_delta.hip and for the host by tests/obs_delta/ (checked against the oracle's consecutive
 // renders without a GPU), in the manner of ctf_step_core.h.
 #pragma once
 #include <stdint.h>
