@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions and ctf_scripted_roles are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles and ctf_scripted_abilities are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -482,6 +482,31 @@ int ctf_scripted_actions(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, ui
 #define CTF_GUARD_ZONE 3
 int ctf_scripted_roles(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t epsilon_q32,
                        uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
+
+/* Scripted opponents that use their TYPE: ctf_scripted_roles with bit i of ability_mask = agent i moves with its type's ability.  Roles,
+ * goal sets Q (the 3 x 3 window of a flag, dil(opp), dil(S)), what is decided before the search (the carrier's goal, a chaser in dil(S)
+ * and a posted guard next to its flag stay) and the exploration rule (same key, counter and tag, uniform on 0..4, applied last) are
+ * ctf_scripted_roles'.  What changes is how an agent MOVES towards Q, by its class, decided from the state the call reads:
+ *   DIGGER   ability bit set and type 3 (miner).  Passable cells are OPEN (0), DESTRUCTIBLE_TILE1 (2) and DESTRUCTIBLE_TILE2 (3);
+ *     blocks, flags and every agent are walls.  Entering a cell costs w = 1 (OPEN), 2 (tile 3: one hit, then the move) or 3 (tile 2:
+ *     two hits, then the move), the counts mine_block and movement_handler give (gridworld_ctf.py:669-690, :577-580).  Goal cells:
+ *     Q & passable.  D(c) = the least sum of entry costs over 4-neighbour paths from c into a goal cell; the goal cell's own cost is
+ *     counted, the start cell's is not, D of a goal cell is 0.  The action is the lowest-numbered of 0..3 whose neighbour n is inside
+ *     the grid, passable and has the minimum finite w(n) + D(n); none: 4.  Moving into a destructible tile IS the mining action, so
+ *     the output is still 0..3.
+ *   VAULTER  ability bit set, type 2 and (hp[a] - VAULT_HP_COST) > VAULT_MIN_HP, evaluated in f64 as the step evaluates it
+ *     (gridworld_ctf.py:649-650).  Passable cells are OPEN only.  Moves: the four unit moves and the jumps 5..8 with deltas (-2,0),
+ *     (2,0), (0,2), (0,-2); a jump needs its landing cell inside the grid and OPEN, the cell jumped over may hold anything (:123-133,
+ *     :643-650).  Every move costs 1, and later jumps are taken to be affordable: the agent plans again at every call, as a walker
+ *     once its hp permits no jump.  The action is the lowest-numbered of 0, 1, 2, 3, 5, 6, 7, 8 whose landing cell has the minimum
+ *     finite D (a walk wins a tie with a jump); none: 4.
+ *   WALKER   everyone else: ctf_scripted_roles' action, bit for bit, whatever the ability bit says.
+ * actions_dev, the stream order and what is read are as for ctf_scripted_actions: one kernel launch and nothing else (none for an
+ * empty mask), capturable; every rng_mode, log_metrics == 0 included; env state is only read.  When ability_mask & agent_mask names no
+ * agent of type 2 or 3, the launch is ctf_scripted_roles' own.
+ * CTF_E_INVALID, before anything is launched: everything ctf_scripted_roles refuses, and an ability_mask bit at or above N. */
+int ctf_scripted_abilities(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask,
+                           uint32_t epsilon_q32, uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

@@ -172,6 +172,7 @@ SYMBOLS = {
     "ctf_random_actions": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_actions": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_roles": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "ctf_scripted_abilities": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),
     "ctf_abi_version": (C.c_int32, []),
     "ctf_sizeof_config": (C.c_int32, []),

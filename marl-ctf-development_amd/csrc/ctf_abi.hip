@@ -850,3 +850,21 @@ extern "C" int ctf_scripted_roles(ctf_env* h, int8_t* actions, uint32_t agent_ma
     HIP_TRY(ctf_launch_scripted_roles(script_args(h->d, h->p), actions, agent_mask, role_pack, epsilon_q32, seed, step, env_offset, (hipStream_t)stream));
     return CTF_OK;
 }
+
+extern "C" int ctf_scripted_abilities(ctf_env* h, int8_t* actions, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask, uint32_t epsilon_q32,
+                                      uint64_t seed, uint32_t step, uint32_t env_offset, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_scripted_abilities: null handle");
+    if (!actions) return fail(CTF_E_INVALID, "ctf_scripted_abilities: null actions");
+    if (h->d.N < 32 && (agent_mask >> h->d.N)) return fail(CTF_E_INVALID, "ctf_scripted_abilities: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    if (h->d.N < 32 && (ability_mask >> h->d.N))
+        return fail(CTF_E_INVALID, "ctf_scripted_abilities: ability_mask 0x%x names an agent >= %d", ability_mask, h->d.N);
+    for (int i = 0; i < 16; i++) {
+        const uint32_t role = scr_role_of(role_pack, i);
+        if (role > CTF_ROLE_GUARD) return fail(CTF_E_INVALID, "ctf_scripted_abilities: unknown role %u of agent %d", role, i);
+        if (role && i >= h->d.N) return fail(CTF_E_INVALID, "ctf_scripted_abilities: a role for agent %d >= %d", i, h->d.N);
+    }
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_scripted_abilities(script_args(h->d, h->p), script_abil(h->d), actions, agent_mask, role_pack, ability_mask, epsilon_q32, seed, step,
+                                          env_offset, (hipStream_t)stream));
+    return CTF_OK;
+}

@@ -1,7 +1,9 @@
-// ctf_scripted.h — the scripted opponents (ctf_scripted_actions, ctf_scripted.hip; ctf_scripted_roles, ctf_scripted_roles.hip): the
-// policies, defined once as plain inline functions that compile for the host and the device.  The kernels call them with one lane per
-// grid ROW; scr_env_actions / scr_env_roles below walk the same functions over an array of rows, one env at a time (the host tests,
-// tests/scripted/scripted_main.cpp and roles_main.cpp).  The runner first; the ROLES (runner, chaser, guard per agent) further down.
+// ctf_scripted.h — the scripted opponents (ctf_scripted_actions, ctf_scripted.hip; ctf_scripted_roles, ctf_scripted_roles.hip;
+// ctf_scripted_abilities, ctf_scripted_abilities.hip): the policies, defined once as plain inline functions that compile for the host
+// and the device.  The kernels call them with one lane per grid ROW; scr_env_actions / scr_env_roles / scr_env_abilities below walk
+// the same functions over an array of rows, one env at a time (the host tests, tests/scripted/scripted_main.cpp, roles_main.cpp and
+// abilities_main.cpp).  The runner first; the ROLES (runner, chaser, guard per agent) further down; the ABILITIES (a miner digs, a
+// vaulter jumps) last.
 //
 // CTF_SCRIPT_RUNNER, agent a of team t, a pure function of the env state (grid, positions, has_flag) and the config:
 //   target   T = flag_pos[t] if has_flag[a], else flag_pos[1 - t]: standing next to T is what the pickup and capture rules test
@@ -285,6 +287,206 @@ static inline void scr_env_roles(const ScriptArgs& A, const uint8_t* grid, const
                     out[i] = (int8_t)scr_action(q.dec, q.b0, q.b1, (int)((word[i] >> 8) & 0xFFu));
                 }
         }
+        for (int i = 0; i < A.N; i++)
+            if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team)
+                out[i] = (int8_t)scr_explore(out[i], epsilon_q32, seed, env, step, (uint32_t)i);
+    }
+}
+
+// ---- ABILITIES (ctf_scripted_abilities, ctf_scripted_abilities.hip): bit i of ability_mask = agent i moves with its type's ability ----
+// Roles, goal sets Q, who is decided before the search and the exploration are those of the ROLES above.  What changes is how an agent
+// moves towards Q, by its CLASS, decided from the state the call reads:
+//   SCR_DIGGER   ability bit and type 3 (miner).  Passable: OPEN, DESTRUCTIBLE_TILE1 (2), DESTRUCTIBLE_TILE2 (3); blocks, flags and
+//                agents are walls.  Entering a cell costs w = 1 (OPEN), 2 (tile 3: one hit, then the move), 3 (tile 2: two hits, then
+//                the move): mine_block and movement_handler (gridworld_ctf.py:669-690, :577-580).  Goals Q & passable.  D(c) = the
+//                least sum of entry costs over 4-neighbour paths from c into a goal cell (the goal's own cost counted, c's not; D of
+//                a goal is 0).  Action: the lowest-numbered of 0..3 whose neighbour n is inside the grid, passable and has the minimum
+//                finite w(n) + D(n); none: 4.  Moving into a destructible tile IS the mining action.
+//   SCR_VAULTER  ability bit, type 2 and (hp - vault_hp_cost) > vault_min_hp in f64, as the step tests it (gridworld_ctf.py:649-650).
+//                Passable: OPEN.  Moves: the four unit moves and the jumps 5..8, deltas (-2,0), (2,0), (0,2), (0,-2); a jump needs its
+//                landing cell inside the grid and OPEN, the cell jumped over may hold anything (:123-133, :643-650).  Every move
+//                costs 1; later jumps are taken to be affordable (the agent plans again every step).  Action: the lowest-numbered of
+//                0, 1, 2, 3, 5, 6, 7, 8 whose landing cell has the minimum finite D (a walk wins a tie with a jump); none: 4.
+//   SCR_WALKER   everyone else: scr_env_roles' result, bit for bit, whatever the ability bit says.
+// A FIELD is now (goal kind of SCR_FIELDS, class).
+//
+// BIT-PARALLEL FORM.  One search serves the three classes.  A passable cell x with D(x) settled EMITS in iteration D(x) + w(x): that
+// is the cost, from any neighbour, of the path that enters x first, so
+//   settled = (the neighbours of the emitting frontier E) & passable & ~seen          D of these cells is this iteration's number
+//   E' = p1 | settled & w1,  p1' = p2 | settled & w2,  p2' = settled & w3             two pending masks per row: emit in 2, in 3
+// and an asker takes the first iteration in which a neighbour of its cell emits (scr_pick's rule on E).  The goals are settled at 0:
+// E = goal & w1, p1 = goal & w2, p2 = goal & w3.  With w2 = w3 = 0 this is the runner's loop, iteration for iteration.  The vaulter's
+// neighbours are the eight cells at distance 1 and 2 along a row or a column (a jump and its reverse need the same thing: the cell
+// landed on is OPEN), and its pick keeps a third bit: 1 = a jump.  An iteration can pass with nothing emitting, so the loop ends on
+// "every asker decided" or "nothing emits and nothing is pending", at most 3 G G + 2 iterations.
+#define SCR_WALKER 0u
+#define SCR_DIGGER 1u
+#define SCR_VAULTER 2u
+#define SCR_CLASSES 3
+#define SCR_ITER_BOUND (3 * CTF_MAX_CELLS + 8)  // not reached: every cell emits once, at most 3 iterations after it settled
+
+struct ScriptAbil {
+    uint32_t type_pack;            // 2 bits per agent
+    int32_t off_hp;                // f64 hp[N] in the record
+    double vault_cost, vault_min;  // VAULT_HP_COST, VAULT_MIN_HP
+};
+static inline ScriptAbil script_abil(const DevCfg& d) { return ScriptAbil{d.type_pack, 0, d.vault_cost, d.vault_min}; }
+// does any asked agent move by an ability, judged by TYPE alone (what a launcher can know)
+static inline bool script_any_ability(const ScriptArgs& A, const ScriptAbil& B, uint32_t agent_mask, uint32_t ability_mask) {
+    for (int i = 0; i < A.N; i++)
+        if ((((agent_mask & ability_mask) >> i) & 1u) && ((B.type_pack >> (2 * i)) & 3u) >= 2u) return true;
+    return false;
+}
+// the class of agent i (record rec, 8-byte aligned)
+CTF_HD uint32_t scr_class(const ScriptAbil& B, const uint8_t* rec, int i, uint32_t ability_mask) {
+    const uint32_t type = (B.type_pack >> (2 * i)) & 3u;
+    const double hp = *(const double*)(rec + B.off_hp + 8 * i);
+    if (!((ability_mask >> i) & 1u)) return SCR_WALKER;
+    if (type == 3u) return SCR_DIGGER;
+    return (type == 2u && (hp - B.vault_cost) > B.vault_min) ? SCR_VAULTER : SCR_WALKER;
+}
+// scr_row_open with the rows of DESTRUCTIBLE_TILE1 (t2) and DESTRUCTIBLE_TILE2 (t3) from the same nine dwords
+CTF_HD void scr_row_tiles(const uint8_t* grid, int G, int GS, int r, uint32_t& open, uint32_t& t2, uint32_t& t3) {
+    const int rr = r < G ? r : G - 1;
+    const int b0 = rr * G, w0 = b0 >> 2, last = (GS >> 2) - 1;
+    const uint32_t* words = (const uint32_t*)grid;
+    uint32_t v[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) v[j] = words[(size_t)(w0 + j < last ? w0 + j : last)];  // all in flight together
+    uint64_t a0 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        a0 |= (uint64_t)scr_zero_bytes(v[j]) << (4 * j);
+        a2 |= (uint64_t)scr_zero_bytes(v[j] ^ 0x02020202u) << (4 * j);
+        a3 |= (uint64_t)scr_zero_bytes(v[j] ^ 0x03030303u) << (4 * j);
+    }
+    const uint32_t cols = r < G ? (G >= 32 ? 0xFFFFFFFFu : (1u << G) - 1u) : 0u;
+    open = (uint32_t)(a0 >> (b0 & 3)) & cols;
+    t2 = (uint32_t)(a2 >> (b0 & 3)) & cols;
+    t3 = (uint32_t)(a3 >> (b0 & 3)) & cols;
+}
+// the cells of a row by entry cost, for a class: w[0] | w[1] | w[2] is what the class may enter
+CTF_HD void scr_class_cost(uint32_t cls, uint32_t open, uint32_t t2, uint32_t t3, uint32_t* w) {
+    w[0] = open;
+    w[1] = cls == SCR_DIGGER ? t3 : 0u;
+    w[2] = cls == SCR_DIGGER ? t2 : 0u;
+}
+
+// a row's search state: the emitting frontier, the two pending masks, what has been settled
+struct ScrFront {
+    uint32_t e, p1, p2, seen;
+};
+// the goals Q of a field, cut to what the class may enter, settled at 0
+CTF_HD ScrFront scr_front(uint32_t Q, const uint32_t* w) { return ScrFront{Q & w[0], Q & w[1], Q & w[2], Q & (w[0] | w[1] | w[2])}; }
+// one iteration of a row: near = E of rows r - 1 | r + 1, far = E of rows r - 2 | r + 2 (0 unless the class jumps)
+CTF_HD void scr_advance(ScrFront& s, uint32_t near, uint32_t far, bool jumps, const uint32_t* w) {
+    const uint32_t side = (s.e << 1) | (s.e >> 1) | (jumps ? (s.e << 2) | (s.e >> 2) : 0u);
+    const uint32_t settled = (side | near | far) & (w[0] | w[1] | w[2]) & ~s.seen;
+    s.seen |= settled;
+    s.e = s.p1 | (settled & w[0]);
+    s.p1 = s.p2 | (settled & w[1]);
+    s.p2 = settled & w[2];
+}
+// scr_pick with the four jumps behind the four walks: b2 = the action is a jump, (b1, b0) = which of the four
+struct ScrPick8 {
+    uint32_t dec, b0, b1, b2;
+};
+CTF_HD void scr_pick8(ScrPick8& k, uint32_t P, uint32_t e, uint32_t up, uint32_t down, uint32_t up2, uint32_t down2, bool jumps) {
+    const uint32_t a0 = up, a1 = down, a2 = e >> 1, a3 = e << 1;
+    const uint32_t j0 = jumps ? up2 : 0u, j1 = jumps ? down2 : 0u, j2 = jumps ? e >> 2 : 0u, j3 = jumps ? e << 2 : 0u;
+    const uint32_t walk = a0 | a1 | a2 | a3, undecided = P & ~k.dec;
+    const uint32_t now_w = walk & undecided, now_j = (j0 | j1 | j2 | j3) & undecided & ~walk;
+    k.b0 |= (now_w & ~a0 & (a1 | ~a2)) | (now_j & ~j0 & (j1 | ~j2));
+    k.b1 |= (now_w & ~a0 & ~a1) | (now_j & ~j0 & ~j1);
+    k.b2 |= now_j;
+    k.dec |= now_w | now_j;
+}
+CTF_HD int scr_action8(uint32_t dec, uint32_t b0, uint32_t b1, uint32_t b2, int pc) {
+    return ((dec >> pc) & 1u) ? (int)(((b2 >> pc) & 1u) * 5u + ((b1 >> pc) & 1u) * 2u + ((b0 >> pc) & 1u)) : 4;
+}
+// the class agent j (word v of scr_agent, class in bits 18..19) shows row r: its cell's bit in dig / vault
+CTF_HD void scr_class_add(uint32_t& dig, uint32_t& vault, uint32_t v, int r) {
+    const uint32_t bit = ((v >> 17) & 1u) && (int)(v & 0xFFu) == r ? 1u << ((v >> 8) & 31u) : 0u, cls = (v >> 18) & 3u;
+    dig |= cls == SCR_DIGGER ? bit : 0u;
+    vault |= cls == SCR_VAULTER ? bit : 0u;
+}
+// the askers of a class among the askers P of a goal kind
+CTF_HD uint32_t scr_class_askers(uint32_t P, uint32_t cls, uint32_t dig, uint32_t vault) {
+    return P & (cls == SCR_DIGGER ? dig : cls == SCR_VAULTER ? vault : ~(dig | vault));
+}
+
+// the search of one field over an array of rows: askers P, goal cells Q (not yet cut to what the class may enter)
+static inline void scr_rows_search8(const uint32_t* open, const uint32_t* t2, const uint32_t* t3, uint32_t cls, const uint32_t* P, const uint32_t* Q,
+                                    ScrPick8* k) {
+    ScrFront s[32];
+    uint32_t w[32][3];
+    const bool jumps = cls == SCR_VAULTER;
+    for (int r = 0; r < 32; r++) {
+        scr_class_cost(cls, open[r], t2[r], t3[r], w[r]);
+        s[r] = scr_front(Q[r], w[r]);
+        k[r] = ScrPick8{0, 0, 0, 0};
+    }
+    for (int n = 0; n < SCR_ITER_BOUND; n++) {
+        uint32_t e[32], left = 0, alive = 0;
+        for (int r = 0; r < 32; r++) e[r] = s[r].e;
+        for (int r = 0; r < 32; r++) {
+            const uint32_t up = r > 0 ? e[r - 1] : 0u, down = r < 31 ? e[r + 1] : 0u;
+            const uint32_t up2 = (jumps && r > 1) ? e[r - 2] : 0u, down2 = (jumps && r < 30) ? e[r + 2] : 0u;
+            scr_pick8(k[r], P[r], e[r], up, down, up2, down2, jumps);
+            left |= P[r] & ~k[r].dec;
+            scr_advance(s[r], up | down, up2 | down2, jumps, w[r]);
+            alive |= s[r].e | s[r].p1 | s[r].p2;
+        }
+        if (!left || !alive) break;
+    }
+}
+
+// scr_env_roles with abilities
+static inline void scr_env_abilities(const ScriptArgs& A, const ScriptAbil& B, const uint8_t* grid, const uint8_t* rec, uint32_t agent_mask,
+                                     uint64_t role_pack, uint32_t ability_mask, uint32_t epsilon_q32, uint64_t seed, uint32_t step, uint32_t env,
+                                     int8_t* out) {
+    uint32_t open[32], t2[32], t3[32], word[CTF_MAX_AGENTS];
+    for (int r = 0; r < 32; r++) scr_row_tiles(grid, A.G, A.GS, r, open[r], t2[r], t3[r]);
+    for (int i = 0; i < A.N; i++) {
+        word[i] = scr_agent(A, rec, i);
+        if (word[i]) word[i] |= scr_class(B, rec, i, ability_mask) << 18;
+    }
+    for (int team = 0; team < 2; team++) {
+        if (!((script_teams(A, agent_mask) >> team) & 1u)) continue;
+        ScrRoles m[32];
+        uint32_t P[SCR_FIELDS][32], Q[SCR_FIELDS][32], dig[32], vault[32];
+        for (int r = 0; r < 32; r++) {
+            m[r] = ScrRoles{0, 0, 0, 0, 0, 0, 0, 0};
+            dig[r] = vault[r] = 0;
+            for (int j = 0; j < A.N; j++) {
+                scr_roles_add(m[r], A, word[j] & 0x3FFFFu, j, r, team, agent_mask, role_pack);
+                scr_class_add(dig[r], vault[r], word[j], r);
+            }
+        }
+        for (int r = 0; r < 32; r++) {
+            const uint32_t o_up = r > 0 ? m[r - 1].opp : 0u, o_down = r < 31 ? m[r + 1].opp : 0u;
+            const uint32_t s_up = r > 0 ? scr_guard_set(m[r - 1]) : 0u, s_down = r < 31 ? scr_guard_set(m[r + 1]) : 0u;
+            uint32_t p[SCR_FIELDS], q[SCR_FIELDS];
+            scr_role_fields(m[r], 0xFFFFFFFFu, r, A.flag_pack, team, scr_dil(o_up, m[r].opp, o_down, A.G, r),
+                            scr_dil(s_up, scr_guard_set(m[r]), s_down, A.G, r), p, q);  // q: the goal sets before any tile is asked for
+            for (int f = 0; f < SCR_FIELDS; f++) P[f][r] = p[f], Q[f][r] = q[f];
+        }
+        for (int i = 0; i < A.N; i++)
+            if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team) out[i] = 4;
+        for (int f = 0; f < SCR_FIELDS; f++)
+            for (uint32_t cls = 0; cls < SCR_CLASSES; cls++) {
+                uint32_t Pc[32], any = 0;
+                for (int r = 0; r < 32; r++) any |= Pc[r] = scr_class_askers(P[f][r], cls, dig[r], vault[r]);
+                if (!any) continue;
+                ScrPick8 k[32];
+                scr_rows_search8(open, t2, t3, cls, Pc, Q[f], k);
+                for (int i = 0; i < A.N; i++)
+                    if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team && (word[i] >> 17) && ((word[i] >> 18) & 3u) == cls &&
+                        scr_role_field(word[i], scr_role_of(role_pack, i), m[0].any) == f) {
+                        const ScrPick8& q = k[word[i] & 0xFFu];
+                        out[i] = (int8_t)scr_action8(q.dec, q.b0, q.b1, q.b2, (int)((word[i] >> 8) & 0xFFu));
+                    }
+            }
         for (int i = 0; i < A.N; i++)
             if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team)
                 out[i] = (int8_t)scr_explore(out[i], epsilon_q32, seed, env, step, (uint32_t)i);

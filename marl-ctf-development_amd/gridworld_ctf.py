@@ -429,8 +429,35 @@ class VecGridworldCtf:
         else is ``scripted_actions``'."""
         return self._scripted("ctf_scripted_roles", self.role_pack(roles), agent_mask, team, out, epsilon, seed, step, env_offset)
 
+    def ability_mask(self, abilities):
+        """``abilities`` — None (every agent), a bit mask or a sequence of agent indices — as ctf_scripted_abilities' ability_mask."""
+        n = self.N_AGENTS
+        if abilities is None:
+            return (1 << n) - 1
+        if isinstance(abilities, (int, np.integer)) and not isinstance(abilities, bool):
+            mask = int(abilities)
+        else:
+            idx = list(abilities)
+            if any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= int(i) < n for i in idx):
+                raise ValueError(f"abilities names an agent outside 0..{n - 1}")
+            mask = sum(1 << int(i) for i in set(idx))
+        if mask < 0 or mask >> n:
+            raise ValueError(f"abilities 0x{mask:x} names an agent outside 0..{n - 1}")
+        return mask
+
+    def scripted_abilities(self, roles, abilities=None, agent_mask=None, team=None, out=None, epsilon=0.0, seed=0, step=None, env_offset=0):
+        """``scripted_roles`` for agents that use their TYPE (include/ctf_env.h, ctf_scripted_abilities): an agent named by
+        ``abilities`` — None: every asked agent; a bit mask; a sequence of agent indices — plans with its type's movement ability.  A
+        miner (type 3) digs: destructible tiles are passable at the cost of the hits they take, and moving into one is the mining
+        action.  A vaulter (type 2) whose hp permits a jump now plans with the jumps 5..8 as well.  Every other agent moves as
+        ``scripted_roles`` moves it, byte for byte.  Everything else is ``scripted_roles``'."""
+        return self._scripted("ctf_scripted_abilities", (self.role_pack(roles), self.ability_mask(abilities)), agent_mask, team, out, epsilon, seed,
+                              step, env_offset)
+
     def _scripted(self, call, what, agent_mask, team, out, epsilon, seed, step, env_offset):
+        """``what``: the call's own arguments between the mask and epsilon (one value or a tuple)"""
         torch = _torch()
+        what = what if isinstance(what, tuple) else (what,)
         if (agent_mask is None) == (team is None):
             raise ValueError("give agent_mask or team (one of them)")
         if team is not None and int(team) not in (0, 1):
@@ -449,7 +476,7 @@ class VecGridworldCtf:
             self._scripted_calls = step + 1
         a = self._check_dev(out, torch.int8, self.n_envs * self.N_AGENTS)
         eps_q32 = min(int(float(epsilon) * 4294967296.0), 0xFFFFFFFF)
-        self._call(call, a, mask, what, eps_q32, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(env_offset) & 0xFFFFFFFF, self._stream())
+        self._call(call, a, mask, *what, eps_q32, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(env_offset) & 0xFFFFFFFF, self._stream())
         return out
 
     def counters(self):

@@ -17,14 +17,17 @@ class ScriptedPolicy:
     """kind "runner": every agent takes a shortest open path to a cell next to the flag it wants — the other team's, or its own once
     it carries one — (breadth-first over open cells; agents, flags and blocks are walls; ties go to the lowest action).
     ``epsilon``: probability of a uniform move on 0..4 instead, from a Philox stream keyed by ``seed`` and indexed by (env, call,
-    agent): the same object replays the same games after ``restart()``."""
+    agent): the same object replays the same games after ``restart()``.  ``abilities``: False keeps the walking bot (today's calls and
+    bytes); True, a bit mask or a sequence of agent indices routes through ``VecGridworldCtf.scripted_abilities``: the named agents
+    (True: all) plan with their type's movement ability — miners dig, vaulters jump."""
 
-    def __init__(self, kind="runner", epsilon=0.0, seed=0):
+    def __init__(self, kind="runner", epsilon=0.0, seed=0, abilities=False):
         if kind not in _abi.SCRIPT_KINDS:
             raise ValueError(f"kind must be one of {sorted(_abi.SCRIPT_KINDS)}")
         if not 0.0 <= float(epsilon) <= 1.0:
             raise ValueError("epsilon must be in [0, 1]")
         self.kind, self.epsilon, self.seed = kind, float(epsilon), int(seed)
+        self.abilities = abilities
         self.calls = 0  # the exploration stream's step index: one per decision
 
     def restart(self):
@@ -32,28 +35,40 @@ class ScriptedPolicy:
 
     def act(self, vec, agent_mask, out=None, env_offset=0):
         """One decision of the agents of ``agent_mask`` in every env of ``vec``, written into ``out`` (int8 [E, N]) in place."""
-        out = vec.scripted_actions(agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls, kind=self.kind,
-                                   env_offset=env_offset)
+        if self.abilities is False:
+            out = vec.scripted_actions(agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls, kind=self.kind,
+                                       env_offset=env_offset)
+        else:
+            out = vec.scripted_abilities([self.kind] * vec.N_AGENTS, self._ability_arg(), agent_mask=agent_mask, out=out, epsilon=self.epsilon,
+                                         seed=self.seed, step=self.calls, env_offset=env_offset)
         self.calls += 1
         return out
+
+
+    def _ability_arg(self):
+        return None if self.abilities is True else self.abilities
 
 
 class ScriptedTeam(ScriptedPolicy):
     """A bot with a ROLE per agent (``VecGridworldCtf.scripted_roles``): ``roles`` is a sequence of N names of "runner", "chaser" and
     "guard", a dict agent -> name (the rest run), or a callable ``cfg -> roles`` resolved against ``vec.cfg`` at the first ``act``
     (``guardians_guard`` below).  It sits wherever a ``ScriptedPolicy`` sits; the agents it decides for are the caller's
-    ``agent_mask``, so one object serves either team."""
+    ``agent_mask``, so one object serves either team.  ``abilities``: as for ``ScriptedPolicy``."""
 
-    def __init__(self, roles, epsilon=0.0, seed=0):
-        super().__init__("runner", epsilon, seed)
+    def __init__(self, roles, epsilon=0.0, seed=0, abilities=False):
+        super().__init__("runner", epsilon, seed, abilities)
         self.roles = roles
         self._resolved = None
 
     def act(self, vec, agent_mask, out=None, env_offset=0):
         if self._resolved is None:
             self._resolved = self.roles(vec.cfg) if callable(self.roles) else self.roles
-        out = vec.scripted_roles(self._resolved, agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls,
-                                 env_offset=env_offset)
+        if self.abilities is False:
+            out = vec.scripted_roles(self._resolved, agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls,
+                                     env_offset=env_offset)
+        else:
+            out = vec.scripted_abilities(self._resolved, self._ability_arg(), agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed,
+                                         step=self.calls, env_offset=env_offset)
         self.calls += 1
         return out
 

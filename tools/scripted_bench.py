@@ -4,6 +4,9 @@ as bench.py staggers them), warm, in ONE process, the variants interleaved call 
   launch  k_step (the yardstick), and the scripted launch for all eight agents and for one team, with epsilon 0 and 0.1
   roles   with --roles: ctf_scripted_roles for both teams and for one — an all-runner pack (ctf_scripted_actions' kernel: the same
           time), all chasers, all guards, and the mix in which the guardians guard and the rest run — next to ctf_scripted_actions
+  abilities  with --abilities: ctf_scripted_abilities for all agents and for one team, an all-runner pack and the guardians_guard mix,
+          ability_mask 0 (ctf_scripted_roles' own launch) and all-ones (the arena has a vaulter and a miner per team), each next to
+          ctf_scripted_roles for the same roles
   duel    a 500-step batched_duel of CtfPolicyNative against the bot, against the same duel between two native networks
 
 HIP-event time per call, medians over --calls calls after warm-up, --reps repetitions; the duels by the host clock round a device
@@ -11,6 +14,7 @@ synchronise.  One JSON document on stdout (and --out).
 
     python tools/scripted_bench.py --out profiles/r16_scripted_bench.json
     python tools/scripted_bench.py --roles --duel-reps 0 --out profiles/r18_scripted_roles_bench.json
+    python tools/scripted_bench.py --abilities --duel-reps 0 --out profiles/r19_scripted_abilities_bench.json
 """
 import argparse
 import importlib
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--duel-steps", type=int, default=500)
     ap.add_argument("--duel-reps", type=int, default=2)
     ap.add_argument("--roles", action="store_true", help="add the ctf_scripted_roles variants to the launch comparison")
+    ap.add_argument("--abilities", action="store_true", help="add the ctf_scripted_abilities variants (and the roles they are compared with)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -75,6 +80,14 @@ def main():
         for name, roles in packs.items():
             variants[f"roles_all_{name}"] = lambda roles=roles: vec.scripted_roles(roles, agent_mask=all_mask, out=bot_acts)
             variants[f"roles_team_{name}"] = lambda roles=roles: vec.scripted_roles(roles, agent_mask=team1, out=bot_acts)
+    if args.abilities:
+        packs = {"runner": ["runner"] * N, "guardians_guard": pkg.scripted.guardians_guard(vec.cfg)}
+        for name, roles in packs.items():
+            for who, mask in (("all", all_mask), ("team", team1)):
+                variants.setdefault(f"roles_{who}_{name}", lambda roles=roles, mask=mask: vec.scripted_roles(roles, agent_mask=mask, out=bot_acts))
+                for bits, abil in (("bits0", 0), ("bits1", all_mask)):
+                    variants[f"abilities_{who}_{name}_{bits}"] = lambda roles=roles, mask=mask, abil=abil: vec.scripted_abilities(
+                        roles, abil, agent_mask=mask, out=bot_acts)
     bench.stagger_phases(vec, torch, 0, gs)
     reps = []
     for _ in range(args.reps):
@@ -90,9 +103,11 @@ def main():
     med = {k: statistics.median(r[k] for r in reps) for k in variants}
     out = dict(envs=E, calls=args.calls, reps=args.reps, device=torch.cuda.get_device_name(0), unit="us per call",
                launch=dict(medians_per_rep=reps, **med, ratio_to_k_step={k: med[k] / med["k_step"] for k in variants if k != "k_step"}))
-    if args.roles:  # every role variant against the runner's launch for the same agents
+    if args.roles or args.abilities:  # every role variant against the runner's launch for the same agents
         out["launch"]["ratio_to_runner"] = {k: med[k] / med["scripted_all_eps0" if k.startswith("roles_all") else "scripted_team_eps0"]
                                             for k in variants if k.startswith("roles_")}
+    if args.abilities:  # every ability variant against ctf_scripted_roles for the same roles and agents
+        out["launch"]["ratio_to_roles"] = {k: med[k] / med["roles_" + k[len("abilities_"):].rsplit("_", 1)[0]] for k in variants if k.startswith("abilities_")}
     assert vec.status() == 0
 
     # the duels: one warm-up duel of a few steps each, then the timed ones, alternating
