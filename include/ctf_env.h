@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles and ctf_scripted_abilities are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles, ctf_scripted_abilities and ctf_scripted_costs are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -507,6 +507,30 @@ int ctf_scripted_roles(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint
  * CTF_E_INVALID, before anything is launched: everything ctf_scripted_roles refuses, and an ability_mask bit at or above N. */
 int ctf_scripted_abilities(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask,
                            uint32_t epsilon_q32, uint64_t seed, uint32_t step, uint32_t env_offset, void* stream);
+
+/* The scripted planners' COST-TO-GO: for every asked agent, how far it is from the goal set its scripted planner heads for, under the
+ * rules that planner moves by — a path cost that knows walls, destructible tiles, jumps and other agents, where a Chebyshev distance
+ * does not.  A potential for reward shaping (F = gamma Phi(s') - Phi(s) leaves the optimal policy alone), a progress measure for
+ * evaluations, a filter for curricula.  Roles (role_pack), classes (ability_mask, type and hp) and goal sets Q (the 3 x 3 window of
+ * a flag, dil(opp), dil(S), before any tile is asked for) are ctf_scripted_abilities'.  cost_dev[e][a] is THE COST OF REACHING Q, not
+ * "the planner's next move + 1":
+ *   0              a is decided before the search (a chaser standing in dil(S), a posted guard next to its flag), or a's own cell
+ *                  lies in Q (a runner next to the flag it wants: ctf_scripted_abilities still moves such an agent, to another open
+ *                  cell of the window, so a cost of 0 does not mean action 4);
+ *   >= 1           the least total entry cost, over move sequences of a's class, from a's cell into a cell of Q the class may enter:
+ *                  WALKER 1 + d(n), the minimum over the four neighbours n; DIGGER w(n) + D(n), the minimum over the four neighbours,
+ *                  with entry costs 1 / 2 / 3; VAULTER 1 + d(n), the minimum over the eight landing cells — the number of steps the
+ *                  planner needs if nothing else moves.  At most 3 G G;
+ *   CTF_COST_NONE  no such sequence exists, or a stands outside the grid (no valid state has one).
+ * With epsilon 0, on the same state and arguments: cost == CTF_COST_NONE implies ctf_scripted_abilities' action 4, cost >= 1 an
+ * action other than 4.  There is no exploration and no seed: the cost is a function of the state.
+ *   cost_dev  int16 [E][N]: written only for the agents whose bit is set in agent_mask; every other entry is left alone
+ * One kernel launch and nothing else (none for an empty mask; one kernel for every role and class): stream-ordered, no allocation,
+ * no synchronisation, capturable.  Works in every rng_mode and with log_metrics == 0; env state is only read.
+ * CTF_E_INVALID, before anything is launched: everything ctf_scripted_abilities refuses, a NULL cost_dev, an odd cost_dev address. */
+#define CTF_COST_NONE (-1)
+int ctf_scripted_costs(ctf_env* env, int16_t* cost_dev /* int16 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask,
+                       void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

@@ -20,6 +20,7 @@ from .duel import batched_duel, batched_tournament  # noqa: F401
 from .harvest import EpisodeHarvest  # noqa: F401
 from .frames import StateRecorder  # noqa: F401
 from .scripted import ScriptedPolicy, ScriptedTeam  # noqa: F401
+from .shaping import PotentialShaping  # noqa: F401
 
 
 def __getattr__(name):  # the policy module needs torch.nn: import it only when asked for

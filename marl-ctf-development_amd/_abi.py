@@ -33,6 +33,7 @@ REVERSE_DEFAULT = 0xFFFFFFFF
 SCRIPT_RUNNER = 0  # ctf_scripted_actions' kinds
 SCRIPT_KINDS = {"runner": SCRIPT_RUNNER}
 SCRIPT_ROLES = {"runner": 0, "chaser": 1, "guard": 2}  # ctf_scripted_roles' CTF_ROLE_*: one nibble of role_pack per agent
+COST_NONE = -1  # ctf_scripted_costs' CTF_COST_NONE: no way to the goal set
 GUARD_ZONE = 3                                         # CTF_GUARD_ZONE
 
 # order of ctf_state_view.metrics rows == the reference's "agent_*" metric names (gridworld_ctf.py:456-468)
@@ -173,6 +174,7 @@ SYMBOLS = {
     "ctf_scripted_actions": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_roles": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_abilities": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "ctf_scripted_costs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),
     "ctf_abi_version": (C.c_int32, []),
     "ctf_sizeof_config": (C.c_int32, []),

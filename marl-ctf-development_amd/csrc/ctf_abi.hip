@@ -868,3 +868,20 @@ extern "C" int ctf_scripted_abilities(ctf_env* h, int8_t* actions, uint32_t agen
                                           env_offset, (hipStream_t)stream));
     return CTF_OK;
 }
+
+extern "C" int ctf_scripted_costs(ctf_env* h, int16_t* costs, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_scripted_costs: null handle");
+    if (!costs) return fail(CTF_E_INVALID, "ctf_scripted_costs: null costs");
+    if ((uintptr_t)costs & 1u) return fail(CTF_E_INVALID, "ctf_scripted_costs: costs is not 2-byte aligned");
+    if (h->d.N < 32 && (agent_mask >> h->d.N)) return fail(CTF_E_INVALID, "ctf_scripted_costs: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    if (h->d.N < 32 && (ability_mask >> h->d.N))
+        return fail(CTF_E_INVALID, "ctf_scripted_costs: ability_mask 0x%x names an agent >= %d", ability_mask, h->d.N);
+    for (int i = 0; i < 16; i++) {
+        const uint32_t role = scr_role_of(role_pack, i);
+        if (role > CTF_ROLE_GUARD) return fail(CTF_E_INVALID, "ctf_scripted_costs: unknown role %u of agent %d", role, i);
+        if (role && i >= h->d.N) return fail(CTF_E_INVALID, "ctf_scripted_costs: a role for agent %d >= %d", i, h->d.N);
+    }
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_scripted_costs(script_args(h->d, h->p), script_abil(h->d), costs, agent_mask, role_pack, ability_mask, (hipStream_t)stream));
+    return CTF_OK;
+}

@@ -492,3 +492,107 @@ static inline void scr_env_abilities(const ScriptArgs& A, const ScriptAbil& B, c
                 out[i] = (int8_t)scr_explore(out[i], epsilon_q32, seed, env, step, (uint32_t)i);
     }
 }
+
+// ---- COSTS (ctf_scripted_costs, ctf_scripted_costs.hip): how far every asked agent is from its goal, under the rules it plans with ----
+// Roles, classes and goal sets Q are those of the ABILITIES above (scr_class, scr_role_field, scr_role_fields with open = all ones).
+// cost(a), an int16, is THE COST OF REACHING Q, not "the planner's next move + 1":
+//   0              a is decided before the search (a chaser standing in dil(S), a posted guard next to its flag), or a's own cell lies
+//                  in Q.  An agent's cell holds its tile and is never passable, so the test is on the uncut Q; such bits are taken out
+//                  of the field's askers as the "decided before the search" bits are.  (The action kernels still MOVE an agent that
+//                  stands in Q — a runner next to the flag steps to another open cell of the window — so cost 0 does not mean action 4.)
+//   n + 1          otherwise: n the 0-based iteration of the search loop in which scr_pick8 decides the asker.  A goal cell of entry
+//                  cost 1 emits in iteration 0, a cell x in iteration D(x) + w(x) - 1, so this is, for the
+//                    WALKER   1 + d(n), the minimum over the four neighbours n, d the BFS distance over OPEN cells,
+//                    DIGGER   w(n) + D(n), the minimum over the four neighbours, entry costs w = 1 / 2 / 3,
+//                    VAULTER  1 + d(n), the minimum over the eight landing cells:
+//                  the least total entry cost over move sequences of a's class from a's cell into a cell of Q the class may enter.
+//   CTF_COST_NONE  no such sequence exists, or a stands outside the grid (no valid state has one).
+// Finite costs are at most 3 G G < 2^15.  No exploration and no seed: the cost is a function of the state.  (CTF_COST_NONE: ctf_env.h)
+
+// the askers of a field for the costs: those of the action rule that do not stand in the (uncut) goal set
+CTF_HD uint32_t scr_cost_askers(uint32_t P, uint32_t Q) { return P & ~Q; }
+// what an iteration adds to a row's decided mask -> the cost its askers latch: n + 1
+CTF_HD int scr_cost_of_iteration(int n) { return n + 1; }
+
+// scr_rows_search8 that keeps WHEN instead of which way: cost[r * 32 + c] = n + 1 for the asker at (r, c) decided in iteration n,
+// CTF_COST_NONE for an asker no iteration decides; the entries of cells without an asker are not written
+static inline void scr_rows_costs8(const uint32_t* open, const uint32_t* t2, const uint32_t* t3, uint32_t cls, const uint32_t* P, const uint32_t* Q,
+                                   int16_t* cost /* [32][32] */) {
+    ScrFront s[32];
+    ScrPick8 k[32];
+    uint32_t w[32][3];
+    const bool jumps = cls == SCR_VAULTER;
+    for (int r = 0; r < 32; r++) {
+        scr_class_cost(cls, open[r], t2[r], t3[r], w[r]);
+        s[r] = scr_front(Q[r], w[r]);
+        k[r] = ScrPick8{0, 0, 0, 0};
+        for (int c = 0; c < 32; c++)
+            if ((P[r] >> c) & 1u) cost[r * 32 + c] = CTF_COST_NONE;
+    }
+    for (int n = 0; n < SCR_ITER_BOUND; n++) {
+        uint32_t e[32], left = 0, alive = 0;
+        for (int r = 0; r < 32; r++) e[r] = s[r].e;
+        for (int r = 0; r < 32; r++) {
+            const uint32_t up = r > 0 ? e[r - 1] : 0u, down = r < 31 ? e[r + 1] : 0u;
+            const uint32_t up2 = (jumps && r > 1) ? e[r - 2] : 0u, down2 = (jumps && r < 30) ? e[r + 2] : 0u;
+            const uint32_t before = k[r].dec;
+            scr_pick8(k[r], P[r], e[r], up, down, up2, down2, jumps);
+            const uint32_t now = k[r].dec & ~before;
+            for (int c = 0; c < 32; c++)
+                if ((now >> c) & 1u) cost[r * 32 + c] = (int16_t)scr_cost_of_iteration(n);
+            left |= P[r] & ~k[r].dec;
+            scr_advance(s[r], up | down, up2 | down2, jumps, w[r]);
+            alive |= s[r].e | s[r].p1 | s[r].p2;
+        }
+        if (!left || !alive) break;
+    }
+}
+
+// One env, rows as an array: out[i] = cost(i) for the agents of agent_mask, every other entry of out untouched
+static inline void scr_env_costs(const ScriptArgs& A, const ScriptAbil& B, const uint8_t* grid, const uint8_t* rec, uint32_t agent_mask, uint64_t role_pack,
+                                 uint32_t ability_mask, int16_t* out) {
+    uint32_t open[32], t2[32], t3[32], word[CTF_MAX_AGENTS];
+    for (int r = 0; r < 32; r++) scr_row_tiles(grid, A.G, A.GS, r, open[r], t2[r], t3[r]);
+    for (int i = 0; i < A.N; i++) {
+        word[i] = scr_agent(A, rec, i);
+        if (word[i]) word[i] |= scr_class(B, rec, i, ability_mask) << 18;
+    }
+    int16_t cost[32 * 32];
+    for (int team = 0; team < 2; team++) {
+        if (!((script_teams(A, agent_mask) >> team) & 1u)) continue;
+        ScrRoles m[32];
+        uint32_t P[SCR_FIELDS][32], Q[SCR_FIELDS][32], dig[32], vault[32];
+        for (int r = 0; r < 32; r++) {
+            m[r] = ScrRoles{0, 0, 0, 0, 0, 0, 0, 0};
+            dig[r] = vault[r] = 0;
+            for (int j = 0; j < A.N; j++) {
+                scr_roles_add(m[r], A, word[j] & 0x3FFFFu, j, r, team, agent_mask, role_pack);
+                scr_class_add(dig[r], vault[r], word[j], r);
+            }
+        }
+        for (int r = 0; r < 32; r++) {
+            const uint32_t o_up = r > 0 ? m[r - 1].opp : 0u, o_down = r < 31 ? m[r + 1].opp : 0u;
+            const uint32_t s_up = r > 0 ? scr_guard_set(m[r - 1]) : 0u, s_down = r < 31 ? scr_guard_set(m[r + 1]) : 0u;
+            uint32_t p[SCR_FIELDS], q[SCR_FIELDS];
+            scr_role_fields(m[r], 0xFFFFFFFFu, r, A.flag_pack, team, scr_dil(o_up, m[r].opp, o_down, A.G, r),
+                            scr_dil(s_up, scr_guard_set(m[r]), s_down, A.G, r), p, q);  // q: the goal sets before any tile is asked for
+            for (int f = 0; f < SCR_FIELDS; f++) P[f][r] = scr_cost_askers(p[f], q[f]), Q[f][r] = q[f];
+        }
+        // asked and inside the grid: 0 unless a search below says otherwise; outside the grid: no cost
+        for (int i = 0; i < A.N; i++)
+            if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team) out[i] = (int16_t)((word[i] >> 17) ? 0 : CTF_COST_NONE);
+        for (int f = 0; f < SCR_FIELDS; f++)
+            for (uint32_t cls = 0; cls < SCR_CLASSES; cls++) {
+                uint32_t Pc[32], any = 0;
+                for (int r = 0; r < 32; r++) any |= Pc[r] = scr_class_askers(P[f][r], cls, dig[r], vault[r]);
+                if (!any) continue;
+                scr_rows_costs8(open, t2, t3, cls, Pc, Q[f], cost);
+                for (int i = 0; i < A.N; i++)
+                    if (((agent_mask >> i) & 1u) && (int)((A.team_mask >> i) & 1u) == team && (word[i] >> 17) && ((word[i] >> 18) & 3u) == cls &&
+                        scr_role_field(word[i], scr_role_of(role_pack, i), m[0].any) == f) {
+                        const int pr = (int)(word[i] & 0xFFu), pc = (int)((word[i] >> 8) & 0xFFu);
+                        if ((Pc[pr] >> pc) & 1u) out[i] = cost[pr * 32 + pc];
+                    }
+            }
+    }
+}

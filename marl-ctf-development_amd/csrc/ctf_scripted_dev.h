@@ -1,4 +1,4 @@
-// ctf_scripted_dev.h — what the scripted kernels (ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip) share on the device: the launch shape and
+// ctf_scripted_dev.h — what the scripted kernels (ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip, ctf_scripted_costs.hip) share on the device: the launch shape and
 // the two cross-lane moves that bring a row the masks of the rows above and below it.
 #pragma once
 #include <hip/hip_runtime.h>

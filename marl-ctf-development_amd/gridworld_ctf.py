@@ -454,6 +454,33 @@ class VecGridworldCtf:
         return self._scripted("ctf_scripted_abilities", (self.role_pack(roles), self.ability_mask(abilities)), agent_mask, team, out, epsilon, seed,
                               step, env_offset)
 
+    def scripted_costs(self, roles=None, abilities=False, agent_mask=None, team=None, out=None):
+        """The scripted planners' cost-to-go (include/ctf_env.h, ctf_scripted_costs) -> int16 [E, N]: for the agents of ``agent_mask``
+        or of ``team`` — exactly one of the two — the cost of reaching the goal set the scripted planner of that role heads for,
+        under the rules it moves by: 0 when the agent stands in the goal set or is decided before the search, the number of steps
+        the planner needs if nothing else moves otherwise, ``_abi.COST_NONE`` (-1) when there is no way.  ``roles``: as for
+        ``scripted_roles``; None: all runners.  ``abilities`` follows ``ScriptedPolicy``: False (everybody walks), True (every agent
+        plans with its type's ability), a bit mask or a sequence of agent indices.  Only the asked agents' entries of ``out`` are
+        written, in place; ``out=None`` uses a buffer this object owns (zero where never written).  One launch, stream-ordered; no
+        exploration, no seed: a function of the state, which is only read."""
+        torch = _torch()
+        pack = 0 if roles is None else self.role_pack(roles)
+        abil = 0 if abilities is False else self.ability_mask(None if abilities is True else abilities)
+        if (agent_mask is None) == (team is None):
+            raise ValueError("give agent_mask or team (one of them)")
+        if team is not None and int(team) not in (0, 1):
+            raise ValueError("team must be 0 or 1")
+        mask = int(agent_mask) if team is None else self.team_mask(team)
+        if mask < 0 or mask >> self.N_AGENTS:
+            raise ValueError(f"agent_mask 0x{mask:x} names an agent outside 0..{self.N_AGENTS - 1}")
+        if out is None:
+            if getattr(self, "_costs_out", None) is None:
+                self._costs_out = torch.zeros((self.n_envs, self.N_AGENTS), dtype=torch.int16, device=self.device)
+            out = self._costs_out
+        c = self._check_dev(out, torch.int16, self.n_envs * self.N_AGENTS)
+        self._call("ctf_scripted_costs", c, mask, pack, abil, self._stream())
+        return out
+
     def _scripted(self, call, what, agent_mask, team, out, epsilon, seed, step, env_offset):
         """``what``: the call's own arguments between the mask and epsilon (one value or a tuple)"""
         torch = _torch()

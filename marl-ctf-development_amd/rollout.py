@@ -241,7 +241,7 @@ class BatchedRolloutCollector:
             self.grid_states = torch.zeros((S, E, vec.N_CHANNELS, g, g), dtype=self.obs_dtype, device=vec.device)
         return use_codes
 
-    def collect(self, agent, opponent, reset=True, handoff=None, handoff_chunk=16):
+    def collect(self, agent, opponent, reset=True, handoff=None, handoff_chunk=16, shaping=None):
         """-> dict with the tensors ``get_single_rollout`` returns, each with an env axis after the slot axis.  In compact
         mode ``grid_codes`` / ``next_grid_codes`` stand in for ``grid_states`` / ``next_grid_state``.
 
@@ -249,7 +249,13 @@ class BatchedRolloutCollector:
         steps the chunk's compact slots (reward, log-prob, value, action, mask; with ``with_observations`` also codes and
         metadata) are all-gathered asynchronously while the next steps run; the returned dict then carries under
         ``"global"`` the same tensors for ALL ranks' envs in global env order ([S, world * E, ...]) plus the gathered
-        ``next_*`` tensors.  Compact mode only (the one-hot planes are 14x the bytes; a learner expands codes per minibatch)."""
+        ``next_*`` tensors.  Compact mode only (the one-hot planes are 14x the bytes; a learner expands codes per minibatch).
+
+        ``shaping``: a ``shaping.PotentialShaping`` — its ``begin`` runs behind the reset (``reset=False`` is then a ValueError: the
+        shaper needs the start state) and, behind every step, ``step``'s columns of the trained agents are added to the stored
+        ``rewards`` (one launch and a few small tensor kernels per step).  None: not one extra launch, not one changed byte."""
+        if shaping is not None and not reset:
+            raise ValueError("collect(shaping=...) needs reset=True: PotentialShaping.begin wants a freshly reset batch")
         torch, vec, A = self.torch, self.vec, self.A
         use_codes = self.preallocate(agent, opponent)
         E, S, g = vec.n_envs, self.T * self.A, vec.GRID_SIZE
@@ -262,6 +268,8 @@ class BatchedRolloutCollector:
         sent = 0
         if reset:
             vec.reset()  # ppo.py:57
+        if shaping is not None:
+            shaping.begin(vec)
         self.dones.zero_()
         done = None
         # the one-launch bookkeeping (ctf_rollout_store_step) takes raw pointers: contiguous uint8 codes / float16 metadata, N <= 16 agents,
@@ -277,6 +285,8 @@ class BatchedRolloutCollector:
                     self._step_native(agent, opponent, t)
                     rewards, done = vec.step(self._env_actions)
                     self.rewards[t * A:(t + 1) * A] = rewards.index_select(1, self.trained_idx).transpose(0, 1)
+                    if shaping is not None:
+                        self.rewards[t * A:(t + 1) * A] += shaping.step(vec, done).index_select(1, self.trained_idx).transpose(0, 1)
                     if handoff is not None and ((t + 1) % handoff_chunk == 0 or t + 1 == self.T):
                         handoff.launch(sent, (t + 1) * A, local)
                         sent = (t + 1) * A
@@ -294,6 +304,8 @@ class BatchedRolloutCollector:
                 self.logprobs[sl] = a_lp
                 rewards, done = vec.step(env_act)
                 self.rewards[sl] = rewards.index_select(1, self.trained_idx).transpose(0, 1)
+                if shaping is not None:
+                    self.rewards[sl] += shaping.step(vec, done).index_select(1, self.trained_idx).transpose(0, 1)
                 if handoff is not None and ((t + 1) % handoff_chunk == 0 or t + 1 == self.T):
                     handoff.launch(sent, (t + 1) * A, local)  # async: runs beside the next steps
                     sent = (t + 1) * A

@@ -44,6 +44,14 @@ class ScriptedPolicy:
         self.calls += 1
         return out
 
+    def costs(self, vec, agent_mask, out=None):
+        """The cost-to-go of the agents of ``agent_mask`` under this bot's own rules (``VecGridworldCtf.scripted_costs`` with its roles
+        and abilities) -> int16 [E, N], only the asked entries of ``out`` written.  A function of the state: no exploration, and
+        ``calls`` does not advance."""
+        return vec.scripted_costs(self._role_arg(vec), self.abilities, agent_mask=agent_mask, out=out)
+
+    def _role_arg(self, vec):
+        return None  # all runners
 
     def _ability_arg(self):
         return None if self.abilities is True else self.abilities
@@ -60,9 +68,13 @@ class ScriptedTeam(ScriptedPolicy):
         self.roles = roles
         self._resolved = None
 
-    def act(self, vec, agent_mask, out=None, env_offset=0):
+    def _role_arg(self, vec):
         if self._resolved is None:
             self._resolved = self.roles(vec.cfg) if callable(self.roles) else self.roles
+        return self._resolved
+
+    def act(self, vec, agent_mask, out=None, env_offset=0):
+        self._role_arg(vec)
         if self.abilities is False:
             out = vec.scripted_roles(self._resolved, agent_mask=agent_mask, out=out, epsilon=self.epsilon, seed=self.seed, step=self.calls,
                                      env_offset=env_offset)
