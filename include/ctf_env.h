@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles, ctf_scripted_abilities and ctf_scripted_costs are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles, ctf_scripted_abilities, ctf_scripted_costs, ctf_action_effects and ctf_random_effective_actions are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -531,6 +531,49 @@ int ctf_scripted_abilities(ctf_env* env, int8_t* actions_dev /* int8 [E][N] */, 
 #define CTF_COST_NONE (-1)
 int ctf_scripted_costs(ctf_env* env, int16_t* cost_dev /* int16 [E][N] */, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask,
                        void* stream);
+
+/* WHAT EACH ACTION WOULD DO in the state as it stands: the `act` part of the step (gridworld_ctf.py:700-732) as a pure function of
+ * the state — grid, position, hp, has_flag, inventory — and the config, for every asked agent i and action a in 0..8.  ctf_action_mask
+ * knows the agent's TYPE only; this knows walls, grid edges, other agents, an empty block inventory, a vaulter whose hp no longer
+ * pays for a jump and a spawn window that refuses a block.  effect(i, a) is a byte of flags: what act(i, a) would do IF AGENT i ACTED
+ * NOW, BEFORE ANYONE ELSE MOVES.  Inside a real step the agents act in a shuffled order, so another agent may move first (or tag
+ * this one out) and the action may then do something else: every multi-agent action mask carries that caveat.
+ *   CTF_EFF_MOVES     the agent's position changes (:577-580)
+ *   CTF_EFF_JUMPS     the move is a vault: actions 5..8, type 2, landing cell open, (hp - VAULT_HP_COST) > VAULT_MIN_HP evaluated in f64
+ *                     as the step evaluates it (:643-657); the hp falls by the cost.  Implies MOVES
+ *   CTF_EFF_PICKS_UP  the move picks the other flag up (:583-591).  Implies MOVES
+ *   CTF_EFF_CAPTURES  the move captures (:594-610, HOME_FLAG_CAPTURE included); a pickup and a capture in one move set both.  Implies MOVES
+ *   CTF_EFF_MINES     a miner hits a destructible tile (:669-690): tile 2 becomes 3, tile 3 becomes open
+ *   CTF_EFF_BREAKS    that hit opens the cell (the tile was 3); the inventory rises by one unless it is at its cap.  Implies MINES
+ *   CTF_EFF_LAYS      a miner lays a block (:659-667: inventory > 0, target open and outside both spawn windows)
+ * Bit 7 is always 0; MOVES, MINES and LAYS exclude one another.  effect == 0: the action leaves grid, positions, hp, flags, inventory
+ * and counters untouched (action 4, actions 5..8 of types 0 and 1, a target outside the grid or neither open nor minable).  An agent
+ * whose position is outside the grid has every effect 0.  Tagging, healing and the shuffle are not part of `act` nor of the effect.
+ *   effects_dev  u8  [E][N][9] or NULL: effects_dev[e][i][a] = effect(i, a)
+ *   mask_dev     u16 [E][N]    or NULL: bit a of mask_dev[e][i] is set iff effect(i, a) != 0; bit 4 and bits 9..15 are never set
+ *                (a caller that wants "stay" legal ORs 0x10 in)
+ * Only the entries of the agents whose bit is set in agent_mask are written; every other byte is left alone.  One kernel launch and
+ * nothing else (none for an empty mask): stream-ordered, no allocation, no synchronisation, capturable.  Works in every rng_mode and
+ * with log_metrics == 0; env state is only read and no status bit is set.
+ * CTF_E_INVALID, before anything is launched: a null handle, both outputs NULL, a mask bit at or above N, an odd mask_dev address. */
+#define CTF_EFF_MOVES 1u
+#define CTF_EFF_JUMPS 2u
+#define CTF_EFF_PICKS_UP 4u
+#define CTF_EFF_CAPTURES 8u
+#define CTF_EFF_MINES 16u
+#define CTF_EFF_BREAKS 32u
+#define CTF_EFF_LAYS 64u
+int ctf_action_effects(ctf_env* env, uint16_t* mask_dev /* u16 [E][N] or NULL */, uint8_t* effects_dev /* u8 [E][N][9] or NULL */,
+                       uint32_t agent_mask, void* stream);
+
+/* A RANDOM OPPONENT THAT NEVER BUMPS INTO A WALL: for each asked agent i of env e, S = its mask under ctf_action_effects' rule.
+ * S empty: action 4, no draw.  Otherwise w = Philox4x32-10(key = (seed lo, seed hi), counter = (env_offset + e, step, i, 0x45464631
+ * "EFF1")), k = (w[0] * popcount(S)) >> 32, and the action is the index of the (k + 1)-th lowest set bit of S.  These are env
+ * actions: they go to ctf_step as they are.  Write discipline (only the asked agents' bytes), stream order, capturability and
+ * refusals are ctf_scripted_actions': one kernel launch and nothing else, CTF_E_INVALID for a null handle, a NULL actions_dev or a
+ * mask bit at or above N. */
+int ctf_random_effective_actions(ctf_env* env, int8_t* actions_dev /* i8 [E][N] */, uint32_t agent_mask, uint64_t seed, uint32_t step,
+                                 uint32_t env_offset, void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

@@ -13,13 +13,13 @@ or, for drop-in use with the reference's own scripts, put this directory first o
 ``from gridworld_ctf import GridworldCtf`` resolves here.
 """
 from . import _abi, config, configs, sharding  # noqa: F401
-from .gridworld_ctf import GridworldCtf, VecGridworldCtf, expand_codes  # noqa: F401
+from .gridworld_ctf import GridworldCtf, VecGridworldCtf, effects_table, expand_codes  # noqa: F401
 from .maps import CtfScenarios  # noqa: F401
 from .rollout import BatchedRolloutCollector  # noqa: F401
 from .duel import batched_duel, batched_tournament  # noqa: F401
 from .harvest import EpisodeHarvest  # noqa: F401
 from .frames import StateRecorder  # noqa: F401
-from .scripted import ScriptedPolicy, ScriptedTeam  # noqa: F401
+from .scripted import ScriptedPolicy, ScriptedTeam, ScriptedWanderer  # noqa: F401
 from .shaping import PotentialShaping  # noqa: F401
 
 

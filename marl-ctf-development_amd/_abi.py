@@ -33,6 +33,11 @@ REVERSE_DEFAULT = 0xFFFFFFFF
 SCRIPT_RUNNER = 0  # ctf_scripted_actions' kinds
 SCRIPT_KINDS = {"runner": SCRIPT_RUNNER}
 SCRIPT_ROLES = {"runner": 0, "chaser": 1, "guard": 2}  # ctf_scripted_roles' CTF_ROLE_*: one nibble of role_pack per agent
+# ctf_action_effects' CTF_EFF_* flags: what an action would do if its agent acted now
+EFF_MOVES, EFF_JUMPS, EFF_PICKS_UP, EFF_CAPTURES, EFF_MINES, EFF_BREAKS, EFF_LAYS = 1, 2, 4, 8, 16, 32, 64
+EFF_FLAGS = {"MOVES": EFF_MOVES, "JUMPS": EFF_JUMPS, "PICKS_UP": EFF_PICKS_UP, "CAPTURES": EFF_CAPTURES, "MINES": EFF_MINES, "BREAKS": EFF_BREAKS,
+             "LAYS": EFF_LAYS}
+EFFECT_TAG = 0x45464631  # CTF_EFFECT_TAG, "EFF1": word 3 of ctf_random_effective_actions' Philox counter
 COST_NONE = -1  # ctf_scripted_costs' CTF_COST_NONE: no way to the goal set
 GUARD_ZONE = 3                                         # CTF_GUARD_ZONE
 
@@ -175,6 +180,8 @@ SYMBOLS = {
     "ctf_scripted_roles": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_abilities": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_scripted_costs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, _P]),
+    "ctf_action_effects": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    "ctf_random_effective_actions": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),
     "ctf_abi_version": (C.c_int32, []),
     "ctf_sizeof_config": (C.c_int32, []),

@@ -885,3 +885,24 @@ extern "C" int ctf_scripted_costs(ctf_env* h, int16_t* costs, uint32_t agent_mas
     HIP_TRY(ctf_launch_scripted_costs(script_args(h->d, h->p), script_abil(h->d), costs, agent_mask, role_pack, ability_mask, (hipStream_t)stream));
     return CTF_OK;
 }
+
+extern "C" int ctf_action_effects(ctf_env* h, uint16_t* mask, uint8_t* effects, uint32_t agent_mask, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_action_effects: null handle");
+    if (!mask && !effects) return fail(CTF_E_INVALID, "ctf_action_effects: both outputs are null");
+    if ((uintptr_t)mask & 1u) return fail(CTF_E_INVALID, "ctf_action_effects: mask is not 2-byte aligned");
+    if (h->d.N < 32 && (agent_mask >> h->d.N)) return fail(CTF_E_INVALID, "ctf_action_effects: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_action_effects(effect_args(h->d, h->p), mask, effects, agent_mask, (hipStream_t)stream));
+    return CTF_OK;
+}
+
+extern "C" int ctf_random_effective_actions(ctf_env* h, int8_t* actions, uint32_t agent_mask, uint64_t seed, uint32_t step, uint32_t env_offset,
+                                            void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_random_effective_actions: null handle");
+    if (!actions) return fail(CTF_E_INVALID, "ctf_random_effective_actions: null actions");
+    if (h->d.N < 32 && (agent_mask >> h->d.N))
+        return fail(CTF_E_INVALID, "ctf_random_effective_actions: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    DeviceScope guard(h->device);
+    HIP_TRY(ctf_launch_random_effective(effect_args(h->d, h->p), actions, agent_mask, seed, step, env_offset, (hipStream_t)stream));
+    return CTF_OK;
+}

@@ -1,11 +1,12 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_observe_delta.hip, ctf_step_direct.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip and ctf_scripted_costs.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_observe_delta.hip, ctf_step_direct.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip, ctf_scripted_costs.hip and ctf_effects.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ctf_device.h"
+#include "ctf_effects.h"
 #include "ctf_harvest.h"
 #include "ctf_scripted.h"
 #include "ctf_snapshot.h"
@@ -80,4 +81,8 @@ hipError_t ctf_launch_scripted_abilities(const ScriptArgs&, const ScriptAbil&, i
 // ---- ctf_scripted_costs.hip (one kernel for every role and class; nothing is launched for an empty mask)
 hipError_t ctf_launch_scripted_costs(const ScriptArgs&, const ScriptAbil&, int16_t* costs, uint32_t agent_mask, uint64_t role_pack, uint32_t ability_mask,
                                      hipStream_t);
+// ---- ctf_effects.hip (one kernel each; nothing is launched for an empty mask)
+hipError_t ctf_launch_action_effects(const EffectArgs&, uint16_t* mask, uint8_t* effects, uint32_t agent_mask, hipStream_t);
+hipError_t ctf_launch_random_effective(const EffectArgs&, int8_t* actions, uint32_t agent_mask, uint64_t seed, uint32_t step, uint32_t env_offset,
+                                       hipStream_t);
 }

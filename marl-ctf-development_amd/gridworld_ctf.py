@@ -481,6 +481,61 @@ class VecGridworldCtf:
         self._call("ctf_scripted_costs", c, mask, pack, abil, self._stream())
         return out
 
+    def _effect_mask(self, agent_mask, team):
+        """the agents of ``agent_mask`` or of ``team``; neither: all agents"""
+        if agent_mask is not None and team is not None:
+            raise ValueError("give agent_mask or team, not both")
+        if team is not None and int(team) not in (0, 1):
+            raise ValueError("team must be 0 or 1")
+        mask = (1 << self.N_AGENTS) - 1 if agent_mask is None and team is None else int(agent_mask) if team is None else self.team_mask(team)
+        if mask < 0 or mask >> self.N_AGENTS:
+            raise ValueError(f"agent_mask 0x{mask:x} names an agent outside 0..{self.N_AGENTS - 1}")
+        return mask
+
+    def effective_actions(self, agent_mask=None, team=None, out=None):
+        """Which actions do anything in the state as it stands (include/ctf_env.h, ctf_action_effects) -> int16 [E, N]: bit a of entry
+        [e, i] is set iff action a of agent i would change something — move it, pick a flag up, capture, mine, lay a block — if the
+        agent acted now, before anyone else moves.  It knows walls, grid edges, other agents, an empty inventory, a vaulter's hp and
+        the spawn windows; bit 4 ("stay") is never set: OR 0x10 in to keep it legal.  Inside a real step another agent may move
+        first: every multi-agent action mask carries that caveat.  ``agent_mask`` (bit i = agent i) or ``team``, neither: all agents;
+        only the asked agents' entries of ``out`` are written, in place; ``out=None`` uses a buffer this object owns (zero where never
+        written).  One launch, stream-ordered; the env is only read.  ``effects_table`` turns the result into a bool table."""
+        torch = _torch()
+        mask = self._effect_mask(agent_mask, team)
+        if out is None:
+            if getattr(self, "_effmask_out", None) is None:
+                self._effmask_out = torch.zeros((self.n_envs, self.N_AGENTS), dtype=torch.int16, device=self.device)
+            out = self._effmask_out
+        m = self._check_dev(out, torch.int16, self.n_envs * self.N_AGENTS)
+        self._call("ctf_action_effects", m, None, mask, self._stream())
+        return out
+
+    def action_effects(self, agent_mask=None, team=None, out=None):
+        """WHAT each action would do (include/ctf_env.h, ctf_action_effects) -> uint8 [E, N, 9]: entry [e, i, a] is a byte of
+        ``_abi.EFF_*`` flags — MOVES, JUMPS, PICKS_UP, CAPTURES, MINES, BREAKS, LAYS — 0 when action a of agent i leaves everything as
+        it is.  Arguments, write discipline and the caveat are ``effective_actions``'."""
+        torch = _torch()
+        mask = self._effect_mask(agent_mask, team)
+        if out is None:
+            if getattr(self, "_effects_out", None) is None:
+                self._effects_out = torch.zeros((self.n_envs, self.N_AGENTS, _abi.N_ACTIONS), dtype=torch.uint8, device=self.device)
+            out = self._effects_out
+        f = self._check_dev(out, torch.uint8, self.n_envs * self.N_AGENTS * _abi.N_ACTIONS)
+        self._call("ctf_action_effects", None, f, mask, self._stream())
+        return out
+
+    def random_effective_actions(self, out, seed, step, agent_mask=None, team=None, env_offset=0):
+        """A uniform draw among the actions that do something (include/ctf_env.h, ctf_random_effective_actions), for the agents of
+        ``agent_mask`` or of ``team`` (neither: all), written into ``out`` (int8 [E, N]) in place, the other agents' bytes left alone:
+        a random walker that never bumps into a wall.  An agent none of whose actions does anything gets 4.  The draw is
+        Philox(seed; env_offset + e, step, agent): the same arguments on the same state give the same actions.  ENV actions: they go
+        to ``step`` as they are.  One launch, stream-ordered; the env is only read."""
+        mask = self._effect_mask(agent_mask, team)
+        a = self._check_dev(out, _torch().int8, self.n_envs * self.N_AGENTS)
+        self._call("ctf_random_effective_actions", a, mask, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(env_offset) & 0xFFFFFFFF,
+                   self._stream())
+        return out
+
     def _scripted(self, call, what, agent_mask, team, out, epsilon, seed, step, env_offset):
         """``what``: the call's own arguments between the mask and epsilon (one value or a tuple)"""
         torch = _torch()
@@ -780,6 +835,17 @@ class VecGridworldCtf:
         return bits.value
 
 
+def effects_table(mask):
+    """``effective_actions``' masks (a tensor or an array of integers, any shape) -> bool [..., 9]: entry a = bit a of the mask, for
+    callers that mask logits (``logits.masked_fill(~table, -inf)``; OR 0x10 into the mask first to keep "stay" legal)."""
+    if isinstance(mask, np.ndarray) or not hasattr(mask, "device"):
+        m = np.asarray(mask).astype(np.int64)
+        return ((m[..., None] >> np.arange(_abi.N_ACTIONS)) & 1).astype(bool)
+    torch = _torch()
+    bits = torch.arange(_abi.N_ACTIONS, device=mask.device, dtype=torch.int32)
+    return ((mask.to(torch.int32).unsqueeze(-1) >> bits) & 1).to(torch.bool)
+
+
 def metrics_from_counters(counters, team_captures, agent_teams, agent_types, n_agents):
     """The reference's metrics dict (gridworld_ctf.py:425-470) without the visitation maps, from agent-level counters
     ``counters[k][i]`` (k in _abi.METRIC_NAMES order) and ``team_captures[t]``: the team_* and agent_type_* entries are sums of
@@ -946,6 +1012,16 @@ class GridworldCtf:
         self._pull()
         if self.MAP_SYMMETRY_CHECK:
             assert np.all(self.standardise_state(0) == self.standardise_state(1, reverse_grid=True))
+
+    def action_effects(self):
+        """What each action of each agent would do in the env's present state (``VecGridworldCtf.action_effects``) -> numpy uint8
+        [N, 9] of ``_abi.EFF_*`` flags; 0: the action changes nothing."""
+        return self._vec.action_effects()[0].cpu().numpy()
+
+    def effective_actions(self):
+        """Which actions do anything in the env's present state (``VecGridworldCtf.effective_actions``) -> numpy int16 [N]: bit a of
+        entry i = action a of agent i changes something if the agent acts before anyone else moves."""
+        return self._vec.effective_actions()[0].cpu().numpy()
 
     def _global_rng_in(self):
         """random / np.random -> the two uint32 [625] arrays (624 words + position) ctf_host_step installs before the step.

@@ -85,6 +85,31 @@ class ScriptedTeam(ScriptedPolicy):
         return out
 
 
+class ScriptedWanderer(ScriptedPolicy):
+    """A random opponent that never bumps into a wall (``VecGridworldCtf.random_effective_actions``): every decision is a uniform
+    draw among the actions that DO something in the state as it stands — a move into an open cell, a jump the hp pays for, a hit on a
+    destructible tile, a block the inventory and the spawn windows allow — from a Philox stream keyed by ``seed`` and indexed by
+    (env, call, agent); an agent with no such action stays.  It sits wherever a ``ScriptedPolicy`` sits and replays the same games
+    after ``restart()``.  It has no goal, so it has no cost-to-go."""
+
+    def __init__(self, seed=0):
+        super().__init__("runner", 0.0, seed, False)
+
+    def act(self, vec, agent_mask, out=None, env_offset=0):
+        if out is None:
+            if getattr(vec, "_scripted_out", None) is None:  # the buffer ``scripted_actions`` hands out (zero where never written)
+                import torch
+
+                vec._scripted_out = torch.zeros((vec.n_envs, vec.N_AGENTS), dtype=torch.int8, device=vec.device)
+            out = vec._scripted_out
+        out = vec.random_effective_actions(out, self.seed, self.calls, agent_mask=agent_mask, env_offset=env_offset)
+        self.calls += 1
+        return out
+
+    def costs(self, vec, agent_mask, out=None):
+        raise NotImplementedError("a wanderer has no goal: there is no cost-to-go")
+
+
 def guardians_guard(cfg):
     """roles for ``ScriptedTeam``: the agents of type 1 (guardians: they hit harder near their own flag) guard, the rest run"""
     return ["guard" if int(cfg.agent_type[i]) == 1 else "runner" for i in range(cfg.n_agents)]
