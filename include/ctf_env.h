@@ -14,7 +14,7 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the null stream); calls that take a
  *     stream only enqueue work on it and return;
  *   - ctf_step, ctf_observe, ctf_observe_codes, ctf_step_observe, ctf_reset, ctf_harvest_episodes, ctf_harvest_visitation,
- *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles, ctf_scripted_abilities, ctf_scripted_costs, ctf_action_effects and ctf_random_effective_actions are kernel launches and nothing else (no
+ *     ctf_export_visitation, ctf_export_states, ctf_import_states, ctf_scripted_actions, ctf_scripted_roles, ctf_scripted_abilities, ctf_scripted_costs, ctf_action_effects, ctf_random_effective_actions and ctf_reset_scattered are kernel launches and nothing else (no
  *     allocation, no copy, no synchronisation, no host-side state that moves from call to call), so a caller may capture them
  *     into a hipGraph on `stream` and replay it: every replay is the next step (tests/test_gpu_hipgraph.py);
  *   - return value 0 = OK, negative = error (see CTF_E_*); `ctf_last_error()` has the text;
@@ -574,6 +574,38 @@ int ctf_action_effects(ctf_env* env, uint16_t* mask_dev /* u16 [E][N] or NULL */
  * mask bit at or above N. */
 int ctf_random_effective_actions(ctf_env* env, int8_t* actions_dev /* i8 [E][N] */, uint32_t agent_mask, uint64_t seed, uint32_t step,
                                  uint32_t env_offset, void* stream);
+
+/* RANDOMISED EPISODE STARTS: ctf_reset with the asked agents drawn onto open cells round their start cells, on the device.  For every
+ * env e whose mask byte is non-zero (NULL = all):
+ *   A. everything ctf_reset does: the grid becomes the init grid; hp, flags and inventories are reset; the step count, the captures
+ *      and `done` are reset; the counters are zeroed; `perm` is kept and both generators are untouched;
+ *   B. placement, for i = 0 .. N - 1 in ascending order.  An agent outside agent_mask stays on s_i = start_pos[i].  For an agent
+ *      inside it the candidate set C_i is {s_i} together with every cell c with init_grid[c] == 0 (OPEN), cheb(c, s_i) <= radius, c
+ *      not taken by an earlier agent of this call and — with CTF_SCATTER_OWN_SIDE — cheb(c, flag_pos[t]) <= cheb(c, flag_pos[1 - t]),
+ *      t the agent's team.  s_i holds an agent tile in the init grid, so it is never OPEN: nobody but i can draw it and n = |C_i| >= 1
+ *      always; there is no failure case and no status bit.  r = round + (episode_dev ? episode_dev[e] : 0), a u32 add that wraps;
+ *      w = Philox4x32-10(key = (seed lo, seed hi), counter = (env_offset + e, r, i, 0x53435431 "SCT1")) — ctf_random_actions'
+ *      generator; k = (w[0] * n) >> 32; the agent's cell is the (k + 1)-th element of C_i in ascending row-major cell index.  Then
+ *      pos[i] = cell, grid[s_i] = 0 and grid[cell] = init_grid[s_i];
+ *   C. with episode_dev, episode_dev[e] += 1 (masked envs only).  Visitation (log_metrics): when every agent stands on its s_i the
+ *      env is left exactly as ctf_reset leaves it; otherwise the base maps are written out — zeros, 1 at each agent's cell — and the
+ *      log is empty: the device form ctf_import_states gives for those maps at step 0.
+ * Envs outside the mask are untouched, their episode_dev entry included.  Any radius >= G - 1 means the whole grid.  radius == 0 or
+ * agent_mask == 0 gives ctf_reset's result bit for bit (k_reset itself is launched; with episode_dev, which k_reset does not know, the
+ * placement kernel with an empty agent mask — the same bytes) and episode_dev is still advanced.
+ * One kernel launch and nothing else: stream-ordered, no allocation, no synchronisation, no host state; capturable behind ctf_step,
+ * and with episode_dev every replay of the graph draws afresh.  Works in every rng_mode and with log_metrics == 0.  A retained
+ * observation buffer needs no ctf_obs_invalidate: this is a state change like ctf_reset.
+ * WHAT IT IS NOT: the reference has no such reset.  A plain ctf_reset, and the in-kernel auto-reset of CTF_STEP_AUTO_RESET, still go
+ * to the config's start cells: a loop that wants scattered starts steps WITHOUT auto-reset and calls this with env_mask_dev =
+ * done_dev, behind the harvests (which only read).
+ * CTF_E_INVALID, before anything is launched: a null handle, radius < 0, a mask bit at or above N, a flag bit other than
+ * CTF_SCATTER_OWN_SIDE, an episode_dev that is not 4-byte aligned. */
+#define CTF_SCATTER_OWN_SIDE 1u
+int ctf_reset_scattered(ctf_env* env, const uint8_t* env_mask_dev /* u8 [E] or NULL = all */,
+                        uint32_t agent_mask, int32_t radius, uint32_t flags,
+                        uint64_t seed, uint32_t round, uint32_t* episode_dev /* u32 [E] or NULL */,
+                        uint32_t env_offset, void* stream);
 
 const char* ctf_last_error(void); /* thread-local */
 int32_t ctf_abi_version(void);

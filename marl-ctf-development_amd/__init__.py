@@ -21,6 +21,7 @@ from .harvest import EpisodeHarvest  # noqa: F401
 from .frames import StateRecorder  # noqa: F401
 from .scripted import ScriptedPolicy, ScriptedTeam, ScriptedWanderer  # noqa: F401
 from .shaping import PotentialShaping  # noqa: F401
+from .starts import ScatteredStarts  # noqa: F401
 
 
 def __getattr__(name):  # the policy module needs torch.nn: import it only when asked for

@@ -38,6 +38,8 @@ EFF_MOVES, EFF_JUMPS, EFF_PICKS_UP, EFF_CAPTURES, EFF_MINES, EFF_BREAKS, EFF_LAY
 EFF_FLAGS = {"MOVES": EFF_MOVES, "JUMPS": EFF_JUMPS, "PICKS_UP": EFF_PICKS_UP, "CAPTURES": EFF_CAPTURES, "MINES": EFF_MINES, "BREAKS": EFF_BREAKS,
              "LAYS": EFF_LAYS}
 EFFECT_TAG = 0x45464631  # CTF_EFFECT_TAG, "EFF1": word 3 of ctf_random_effective_actions' Philox counter
+SCATTER_OWN_SIDE = 1  # ctf_reset_scattered's CTF_SCATTER_OWN_SIDE: draw only cells no further from the own flag than from the other
+SCATTER_TAG = 0x53435431  # CTF_SCATTER_TAG, "SCT1": word 3 of ctf_reset_scattered's Philox counter
 COST_NONE = -1  # ctf_scripted_costs' CTF_COST_NONE: no way to the goal set
 GUARD_ZONE = 3                                         # CTF_GUARD_ZONE
 
@@ -182,6 +184,7 @@ SYMBOLS = {
     "ctf_scripted_costs": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, _P]),
     "ctf_action_effects": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     "ctf_random_effective_actions": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "ctf_reset_scattered": (C.c_int, [_P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P]),
     "ctf_last_error": (C.c_char_p, []),
     "ctf_abi_version": (C.c_int32, []),
     "ctf_sizeof_config": (C.c_int32, []),

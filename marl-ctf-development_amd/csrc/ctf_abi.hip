@@ -906,3 +906,20 @@ extern "C" int ctf_random_effective_actions(ctf_env* h, int8_t* actions, uint32_
     HIP_TRY(ctf_launch_random_effective(effect_args(h->d, h->p), actions, agent_mask, seed, step, env_offset, (hipStream_t)stream));
     return CTF_OK;
 }
+
+// ---- randomised episode starts (ctf_scatter.h / ctf_scatter.hip) -------------------------------------------------------------------
+extern "C" int ctf_reset_scattered(ctf_env* h, const uint8_t* mask_dev, uint32_t agent_mask, int32_t radius, uint32_t flags, uint64_t seed, uint32_t round,
+                                   uint32_t* episode_dev, uint32_t env_offset, void* stream) {
+    if (!h) return fail(CTF_E_INVALID, "ctf_reset_scattered: null handle");
+    if (radius < 0) return fail(CTF_E_INVALID, "ctf_reset_scattered: radius %d < 0", radius);
+    if (h->d.N < 32 && (agent_mask >> h->d.N)) return fail(CTF_E_INVALID, "ctf_reset_scattered: agent_mask 0x%x names an agent >= %d", agent_mask, h->d.N);
+    if (flags & ~CTF_SCATTER_OWN_SIDE) return fail(CTF_E_INVALID, "ctf_reset_scattered: unknown flags 0x%x", flags);
+    if ((uintptr_t)episode_dev & 3u) return fail(CTF_E_INVALID, "ctf_reset_scattered: episode_dev is not 4-byte aligned");
+    DeviceScope guard(h->device);
+    const bool plain = radius == 0 || agent_mask == 0;  // nobody can move: ctf_reset's result
+    if (plain && !episode_dev) HIP_TRY(ctf_launch_reset(h->d, h->p, mask_dev, 0, (hipStream_t)stream));
+    else  // (k_reset knows no episode counter: the placement kernel with nobody asked writes the same bytes and advances it, in one launch)
+        HIP_TRY(ctf_launch_reset_scattered(scatter_args(h->d, h->p), mask_dev, plain ? 0u : agent_mask, radius, flags, seed, round, episode_dev, env_offset,
+                                           (hipStream_t)stream));
+    return CTF_OK;
+}

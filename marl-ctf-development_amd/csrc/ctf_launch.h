@@ -1,5 +1,5 @@
 // ctf_launch.h — the launch interface between the translation units of the env side: everything ctf_abi.hip calls in
-// ctf_kernels.hip, ctf_observe_delta.hip, ctf_step_direct.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip, ctf_scripted_costs.hip and ctf_effects.hip.  Every file that defines or calls one of these includes
+// ctf_kernels.hip, ctf_observe_delta.hip, ctf_step_direct.hip, ctf_rng.hip, ctf_snapshot.hip, ctf_harvest.hip, ctf_visitation.hip, ctf_states.hip, ctf_scripted.hip, ctf_scripted_roles.hip, ctf_scripted_abilities.hip, ctf_scripted_costs.hip, ctf_effects.hip and ctf_scatter.hip.  Every file that defines or calls one of these includes
 // this header, so a parameter list cannot drift between them unnoticed (the names have C linkage: a mismatch would link).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include "ctf_device.h"
 #include "ctf_effects.h"
 #include "ctf_harvest.h"
+#include "ctf_scatter.h"
 #include "ctf_scripted.h"
 #include "ctf_snapshot.h"
 #include "ctf_states.h"
@@ -85,4 +86,7 @@ hipError_t ctf_launch_scripted_costs(const ScriptArgs&, const ScriptAbil&, int16
 hipError_t ctf_launch_action_effects(const EffectArgs&, uint16_t* mask, uint8_t* effects, uint32_t agent_mask, hipStream_t);
 hipError_t ctf_launch_random_effective(const EffectArgs&, int8_t* actions, uint32_t agent_mask, uint64_t seed, uint32_t step, uint32_t env_offset,
                                        hipStream_t);
+// ---- ctf_scatter.hip (one kernel; the caller sends radius 0 / an empty agent mask without an episode counter to ctf_launch_reset)
+hipError_t ctf_launch_reset_scattered(const ScatterArgs&, const uint8_t* mask, uint32_t agent_mask, int32_t radius, uint32_t flags, uint64_t seed,
+                                      uint32_t round, uint32_t* episode, uint32_t env_offset, hipStream_t);
 }

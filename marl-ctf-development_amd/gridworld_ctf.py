@@ -316,6 +316,24 @@ class VecGridworldCtf:
         ptr = None if mask is None else self._check_dev(mask, _torch().uint8, self.n_envs)
         self._call("ctf_reset", ptr, self._stream())
 
+    def reset_scattered(self, mask=None, radius=1, agent_mask=None, team=None, own_side=False, seed=0, round=0, episodes=None, env_offset=0):
+        """``reset`` with RANDOMISED STARTS (include/ctf_env.h, ctf_reset_scattered): the agents of ``agent_mask`` (bit i = agent i) or of
+        ``team`` — neither: all — are drawn uniformly onto an open cell within Chebyshev distance ``radius`` of their start cell (or stay
+        on it), one after the other so that no two share a cell; ``own_side`` keeps them no further from their own flag than from the
+        other one.  Everything else is ``reset``'s: hp, flags, inventories, counters; ``perm`` and the generators stay.  The draw is
+        Philox(seed; env_offset + e, round + episodes[e], agent): ``episodes`` (uint32 [E] on the device, or None) is advanced by one
+        for every env of ``mask`` (uint8 [E], None = all), so a loop — or a captured graph — that passes the same arguments draws
+        afresh every time.  ``radius=0`` or an empty agent mask is ``reset`` bit for bit.  One launch, stream-ordered.  The reference
+        has no such reset; ``step(auto_reset=True)`` still goes to the config's start cells."""
+        torch = _torch()
+        agents = self._effect_mask(agent_mask, team)
+        if int(radius) < 0:
+            raise ValueError("radius must be >= 0")
+        ptr = None if mask is None else self._check_dev(mask, torch.uint8, self.n_envs)
+        ep = None if episodes is None else self._check_dev(episodes, torch.uint32, self.n_envs)
+        self._call("ctf_reset_scattered", ptr, agents, min(int(radius), 0x7FFFFFFF), _abi.SCATTER_OWN_SIDE if own_side else 0, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                   int(round) & 0xFFFFFFFF, ep, int(env_offset) & 0xFFFFFFFF, self._stream())
+
     def step(self, actions, auto_reset=False, want_f64=False):
         """actions: int8 CUDA tensor [E, N].  -> (rewards float32 [E, N], done uint8 [E]) (views of
         this object's buffers).  With want_f64 the float64 rewards are also written to ``rewards64``."""

@@ -241,7 +241,7 @@ class BatchedRolloutCollector:
             self.grid_states = torch.zeros((S, E, vec.N_CHANNELS, g, g), dtype=self.obs_dtype, device=vec.device)
         return use_codes
 
-    def collect(self, agent, opponent, reset=True, handoff=None, handoff_chunk=16, shaping=None):
+    def collect(self, agent, opponent, reset=True, handoff=None, handoff_chunk=16, shaping=None, starts=None):
         """-> dict with the tensors ``get_single_rollout`` returns, each with an env axis after the slot axis.  In compact
         mode ``grid_codes`` / ``next_grid_codes`` stand in for ``grid_states`` / ``next_grid_state``.
 
@@ -253,7 +253,13 @@ class BatchedRolloutCollector:
 
         ``shaping``: a ``shaping.PotentialShaping`` — its ``begin`` runs behind the reset (``reset=False`` is then a ValueError: the
         shaper needs the start state) and, behind every step, ``step``'s columns of the trained agents are added to the stored
-        ``rewards`` (one launch and a few small tensor kernels per step).  None: not one extra launch, not one changed byte."""
+        ``rewards`` (one launch and a few small tensor kernels per step).  None: not one extra launch, not one changed byte.
+
+        ``starts``: a ``starts.ScatteredStarts`` — the reset becomes ``starts.reset(vec)``: every env starts its episode with the agents
+        drawn round their start cells, afresh at every collect (``reset=False`` is a ValueError).  ``shaping.begin`` keeps a per-env
+        start potential, so the two compose.  None: ``vec.reset()`` as before — not one extra launch, not one changed byte."""
+        if starts is not None and not reset:
+            raise ValueError("collect(starts=...) needs reset=True: the scattered starts are a reset")
         if shaping is not None and not reset:
             raise ValueError("collect(shaping=...) needs reset=True: PotentialShaping.begin wants a freshly reset batch")
         torch, vec, A = self.torch, self.vec, self.A
@@ -266,7 +272,9 @@ class BatchedRolloutCollector:
         if use_codes:
             local["grid_codes"] = self.grid_codes
         sent = 0
-        if reset:
+        if reset and starts is not None:
+            starts.reset(vec)
+        elif reset:
             vec.reset()  # ppo.py:57
         if shaping is not None:
             shaping.begin(vec)

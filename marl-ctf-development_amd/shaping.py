@@ -22,7 +22,10 @@ class PotentialShaping:
         Phi_prev = where(done & auto_reset, Phi_start, Phi')
 
     Without auto-reset an env that runs on past its end then gets F = 0.  With auto-reset the next episode starts from ``Phi_start``,
-    the potential ``begin`` saw: ``ctf_reset`` draws nothing and restores the start cells, so every episode starts in that state.
+    the potential ``begin`` saw: ``step(auto_reset=True)`` ASSUMES CONFIG STARTS — the in-kernel reset, like ``ctf_reset``, draws
+    nothing and restores the config's start cells, so an auto-reset episode starts in the state ``begin`` saw when that was a plain
+    ``reset``.  ``Phi_start`` is kept per env, so ``begin`` behind ``reset_scattered`` (``collect(starts=...)``, which steps without
+    auto-reset) is as exact: every env's first F is measured from its own start.
     With gamma = 1 the F of an episode sum to ``scale * min(cost(s0), cap)`` exactly."""
 
     def __init__(self, bot, agent_mask, gamma=0.99, scale=1.0, cap=None):
